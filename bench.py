@@ -5,6 +5,11 @@ layers on the 43x43 coarse grid, two SpectralConv2d decoder layers at 141x141).
 
     python bench.py --gpus N --steps K --warmup W [--batch B_per_gpu] [--scaling weak|strong --global-batch G]
                     [--workload ...] [--loss mse|weighted_l2] [--precision f16x2|bf16x3|f32|bf16x2|bf16]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line; ``--full`` adds the other legs (fp32-MFMA timed
+run, roofline and per-kernel table, CPU baseline, accuracy run, strong-scaling legs, quoted parity records).
+``--dump-outputs DIR`` writes the last timed step's loss, updated parameters and gradients as DIR/<name>.npy.
 
 A step = forward + loss + backward + (gradient all-reduce) + clip_grad_norm_(0.99) + Adam on one batch of
 synthetic tensors already resident in HBM (the recipe of the reference's examples/ex2_memory_profile.py:58-71
@@ -13,7 +18,7 @@ the reference's always-on p=0.5 attention dropout.  Operands, accumulators and r
 run in the library's default arithmetic (``f16x2``: every fp32 operand value as two fp16 terms under an in-kernel
 power-of-two scale, three products on the f16 MFMA pipe, fp32 accumulation -- the mode the 1e-5 parity tests run in;
 ``bf16x3`` = three bf16 terms / six products, the default of rounds 2-3, is still selectable); ``--precision f32``
-selects the bit-exact fp32 MFMA kernels, and the default run reports both.
+selects the bit-exact fp32 MFMA kernels, and a ``--full`` run reports both.
 
 One process per GPU (launched by torch.distributed.run for N>1), batch-sharded data parallel: the per-GPU batch is
 fixed (``--scaling weak``, the default) or the global batch is (``--scaling strong --global-batch G``); one flat
@@ -599,11 +604,11 @@ def x3_name(key: str) -> bool:
     return key.startswith("gemm_x3")
 
 
-def cpu_baseline_leg(model_cpu_sd, cfg, budget_s=20.0):
+def cpu_baseline_leg(model_cpu_sd, cfg, budget_s=20.0, reference_model=None):
     """CPU training step on this host's cores, B=4 (the reference default batch): 1 warm-up + as many steps as fit
-    the budget (>= 3).  kind "reference" = the reference's own modules (only where /root/reference exists, i.e. the
-    build container); kind "port" = oracle/galerkin_oracle.py, the pinned CPU restatement -- its step is slightly
-    LIGHTER than the reference's (it treats every nn.Dropout as identity; the always-on attention dropout is kept)."""
+    the budget (>= 3).  kind "reference" = the reference's own modules (`reference_model`: its model module, handed in by
+    tools/cpu_baseline_reference.py); kind "port" = oracle/galerkin_oracle.py, the pinned CPU restatement -- its step is
+    slightly LIGHTER than the reference's (it treats every nn.Dropout as identity; the always-on attention dropout is kept)."""
     B = 4
     # torch's CPU kernels stop scaling (and then regress) well below the core count of a GPU host:
     # cap the thread pool; "cores" in the output is the number of threads actually used
@@ -611,11 +616,9 @@ def cpu_baseline_leg(model_cpu_sd, cfg, budget_s=20.0):
     b = synthetic_batch(B, torch.device("cpu"), seed=7)
     node, pos, grid, target = b["node"], b["pos"], b["grid"], b["target"]
     kind = "port"
-    if os.path.isdir("/root/reference/libs"):
+    if reference_model is not None:
         try:
-            sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-            from make_golden import import_reference
-            _, M, _ = import_reference()
+            M = reference_model
             mc = dict(cfg)
             model = M.FourierTransformer2D(**mc).train()
             opt = torch.optim.Adam(model.parameters(), lr=1e-3)
@@ -628,7 +631,7 @@ def cpu_baseline_leg(model_cpu_sd, cfg, budget_s=20.0):
                 opt.step()
             kind = "reference"
         except Exception as e:                                        # fall back to the port
-            print(f"[bench] reference import failed ({type(e).__name__}: {e}); timing the oracle", file=sys.stderr)
+            print(f"[bench] reference model failed ({type(e).__name__}: {e}); timing the oracle", file=sys.stderr)
             kind = "port"
     if kind == "port":
         from oracle import galerkin_oracle as O
@@ -641,7 +644,7 @@ def cpu_baseline_leg(model_cpu_sd, cfg, budget_s=20.0):
         step()
         n += 1
     dt = time.perf_counter() - t0
-    src = ("the reference's FourierTransformer2D imported from /root/reference" if kind == "reference" else
+    src = ("the reference's own FourierTransformer2D" if kind == "reference" else
            "oracle/galerkin_oracle.py (every nn.Dropout = identity, attention dropout kept: a slightly lighter step "
            "than the reference's)")
     return dict(value=round(B * n / dt, 3), unit="samples/s", cores=torch.get_num_threads(), kind=kind,
@@ -778,6 +781,35 @@ DTYPE_TEXT = {
 }
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20                    # values kept of an array that does not fit the budget
+
+
+def dump_outputs(tr, model, out_dir):
+    """--dump-outputs: what the last timed step handed back to its caller -- the loss, every parameter after the clip + Adam
+    update, and the gradient the backward left in each parameter's .grad -- as float32 <out_dir>/<name>.npy
+    (loss.npy, param.<name>.npy, grad.<name>.npy).  Two runs with the same arguments start from the same seeded inputs and
+    weights, so their dumps compare array by array.  Should the arrays exceed 64 MiB in all, each one beyond the budget is
+    replaced by a fixed, seeded sample of DUMP_SAMPLE of its flattened values (the same positions in every run)."""
+    import numpy as np
+    torch.cuda.synchronize()
+    arrays = [("loss", tr.loss)]
+    named = list(model.named_parameters())
+    arrays += [("param." + k, p) for k, p in named]
+    arrays += [("grad." + k, p.grad) for k, p in named if p.grad is not None]
+    os.makedirs(out_dir, exist_ok=True)
+    used = 0
+    for i, (name, t) in enumerate(arrays):
+        v = t.detach().float().cpu().numpy().astype(np.float32, copy=False)
+        if used + v.nbytes > DUMP_BUDGET_BYTES and v.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(i).choice(v.size, DUMP_SAMPLE, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+        used += v.nbytes
+    if used > DUMP_BUDGET_BYTES:
+        raise SystemExit(f"--dump-outputs: {used} bytes written, over the {DUMP_BUDGET_BYTES}-byte budget")
+
+
 def strong_leg(tr, G, per_gpu, steps, warmup, world, rank, workload, dev):
     """The same step at a FIXED global batch G split evenly over the ranks (north_star: strong scaling) -- a second timed
     region of the same process on a fresh synthetic batch of G / world samples per rank, same model and optimizer state
@@ -822,11 +854,16 @@ def main():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-accuracy", action="store_true", help="skip the short convergence run (val rel-L2)")
     ap.add_argument("--no-f32-leg", action="store_true", help="skip the extra timed run in the exact fp32 MFMA mode")
-    ap.add_argument("--table", default=None, help="write the per-kernel event table to this JSON file")
+    ap.add_argument("--table", default=None, help="with --full: write the per-kernel event table to this JSON file")
     ap.add_argument("--strong-global-batch", default="512", help="comma list: global batches of the extra strong-scaling "
                     "legs every --scaling weak run adds to its line (each split evenly over the ranks; '' or 0: none)")
     ap.add_argument("--comm-in-graph", action="store_true", help="N > 1: capture the RCCL all-reduce inside the step graph "
                     "(one replay per step); falls back to the two-graph form when the capture fails")
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline figure: the fp32-MFMA "
+                    "timed run, roofline / per-kernel table, CPU baseline, accuracy run, strong-scaling legs and the quoted "
+                    "parity records (each still subject to its --no-* switch); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last "
+                    "step returned to its caller (loss, updated parameters, their gradients) as DIR/<name>.npy")
     a = ap.parse_args()
 
     rank = int(os.environ.get("RANK", 0))
@@ -880,10 +917,12 @@ def main():
                 "in_graph": bool(tr.one_graph)}
     elapsed = timed_run(tr, a.steps, a.warmup, world, comm_rec=comm)
     loss = float(tr.loss.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(tr, model, a.dump_outputs)
 
     # the same timed region once more in the bit-exact fp32 MFMA arithmetic (new captures, same weights trajectory)
     f32_leg = None
-    if precision != "f32" and not a.no_f32_leg:
+    if a.full and precision != "f32" and not a.no_f32_leg:
         gt.set_precision("f32")
         tr.g_fb = tr.g_opt = None
         g2 = tr.capture(warm=1)
@@ -893,13 +932,13 @@ def main():
         gt.set_precision(precision)
 
     roof, table = (None, {})
-    if rank == 0 and not a.no_roofline:
+    if a.full and rank == 0 and not a.no_roofline:
         try:
             roof, table = roofline_leg(tr, precision, a.workload)
         except Exception as e:
             print(f"[bench] roofline leg failed: {type(e).__name__}: {e}", file=sys.stderr)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.workload == "ex2_darcy141":
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.workload == "ex2_darcy141":
         try:
             cpu = cpu_baseline_leg(cpu_sd, cfg)
             try:        # the reference implementation itself, timed where /root/reference exists (tools/cpu_baseline_reference.py)
@@ -910,7 +949,7 @@ def main():
         except Exception as e:
             print(f"[bench] cpu baseline failed: {type(e).__name__}: {e}", file=sys.stderr)
     acc = None
-    if rank == 0 and world == 1 and not a.no_accuracy and a.workload == "ex2_darcy141":
+    if a.full and rank == 0 and world == 1 and not a.no_accuracy and a.workload == "ex2_darcy141":
         try:
             acc = accuracy_leg(precision)
         except Exception as e:
@@ -919,7 +958,7 @@ def main():
         dist.barrier()
     # strong-scaling legs (every rank takes part): the fixed global batches G next to the weak-scaling value of the line
     strong = []
-    if a.scaling == "weak" and a.strong_global_batch not in ("", "0"):
+    if a.full and a.scaling == "weak" and a.strong_global_batch not in ("", "0"):
         for G in [int(x) for x in a.strong_global_batch.split(",") if x.strip()]:
             if G <= 0 or G % world:
                 continue
@@ -948,7 +987,7 @@ def main():
             "f32_mfma_exact": f32_leg,
             # algorithmic work of the whole step (19.3 GFLOP per sample fwd + bwd) over the step time
             "useful_tflops": (round(19.3e9 * gb / (elapsed / a.steps) / 1e12, 2) if a.workload == "ex2_darcy141" else None),
-            "roofline": roof, "cpu_baseline": cpu, "parity": parity_record(), "accuracy": acc,
+            "roofline": roof, "cpu_baseline": cpu, "parity": (parity_record() if a.full else None), "accuracy": acc,
             # N > 1: where the exchange step's time went; every N: the same step at fixed global batches (strong scaling:
             # speed-up at N GPUs = strong[i].value of the N-GPU line / strong[i].value of the 1-GPU line)
             "comm": comm, "strong": strong or None,

@@ -368,7 +368,7 @@ def test_bench_two_ranks_on_one_gpu_gloo(gpu_device):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo",
-           "--batch", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--strong-global-batch", "8"]      # roofline + f32 legs stay on:
+           "--batch", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--strong-global-batch", "8"]  # roofline + f32 legs on:
     # rank 0's profiling step must not enter a collective the other rank never joins
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -416,7 +416,7 @@ def test_bench_eight_ranks_on_one_gpu_gloo(gpu_device):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", "29551", os.path.join(root, "bench.py"), "--gpus", "8", "--backend", "gloo", "--batch", "2",
            "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-roofline", "--no-f32-leg", "--no-accuracy",
-           "--strong-global-batch", "8", "--comm-in-graph"]
+           "--strong-global-batch", "8", "--comm-in-graph", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]

@@ -20,7 +20,14 @@ if load1 > 1.0 and os.environ.get("GT_CPU_BASELINE_FORCE") != "1":
 
 model, cfg = bench.build_model("ex2_darcy141")
 sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
-rec = bench.cpu_baseline_leg(sd, cfg, budget_s=float(sys.argv[1]) if len(sys.argv) > 1 else 25.0)
+ref_model = None
+try:
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    from make_golden import import_reference
+    _, ref_model, _ = import_reference()
+except Exception as e:                                  # bench.cpu_baseline_leg then times the oracle port
+    print(f"reference import failed ({type(e).__name__}: {e})", file=sys.stderr)
+rec = bench.cpu_baseline_leg(sd, cfg, budget_s=float(sys.argv[1]) if len(sys.argv) > 1 else 25.0, reference_model=ref_model)
 rec["host"] = {"cpu": platform.processor() or platform.machine(), "logical_cores": os.cpu_count(), "torch_threads": torch.get_num_threads(),
                "where": "build container (no GPU)",
                "loadavg_1min_before": round(load1, 2), "loadavg_1min_after": round(os.getloadavg()[0], 2)}

@@ -10,7 +10,7 @@ cd $R
 export TMPDIR=/tmp
 has() { [[ " $WHAT " == *" $1 "* ]]; }
 if has tests; then ( time timeout 900 python -m pytest tests -m gpu -q ) > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log; fi
-if has bench; then ( time timeout 900 python bench.py --table $O/table.json ) > $O/bench.log 2> $O/bench.err; tail -1 $O/bench.log | cut -c1-600; fi
+if has bench; then ( time timeout 900 python bench.py --full --table $O/table.json ) > $O/bench.log 2> $O/bench.err; tail -1 $O/bench.log | cut -c1-600; fi
 if has prof; then   # one stream (GT_DUAL_STREAM=0): per-kernel averages of kernels that do not overlap
   cd /tmp
   GT_DUAL_STREAM=0 timeout 900 rocprofv3 --kernel-trace --stats -d $O/prof -o trace --output-format csv -- \
@@ -39,10 +39,10 @@ fi
 if has sweep; then
   echo "[" > $O/sweep.json
   for B in 4 16 64 128 256; do
-    timeout 300 python bench.py --batch $B --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-accuracy 2>/dev/null | tail -1 >> $O/sweep.json
+    timeout 300 python bench.py --full --batch $B --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-accuracy 2>/dev/null | tail -1 >> $O/sweep.json
     echo "," >> $O/sweep.json
   done
-  timeout 300 python bench.py --batch 4 --no-graph --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-accuracy 2>/dev/null | tail -1 >> $O/sweep.json
+  timeout 300 python bench.py --full --batch 4 --no-graph --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-accuracy 2>/dev/null | tail -1 >> $O/sweep.json
   echo "]" >> $O/sweep.json
   python - <<PY
 import json
@@ -52,10 +52,10 @@ PY
 fi
 if has work; then
   for w in ex2_darcy211_fourier ex3_darcy_inv ex4_ns ex1_burgers; do
-    timeout 400 python bench.py --workload $w --steps 5 --warmup 2 --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 > $O/bench_$w.json
+    timeout 400 python bench.py --full --workload $w --steps 5 --warmup 2 --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 > $O/bench_$w.json
     python -c "import json; r=json.load(open('$O/bench_$w.json')); print('$w', r['value'], r['ms_per_step'], (r.get('f32_mfma_exact') or {}).get('value'))"
   done
-  timeout 400 python bench.py --loss weighted_l2 --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-accuracy 2>/dev/null | tail -1 > $O/bench_weighted_l2.json
+  timeout 400 python bench.py --full --loss weighted_l2 --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-accuracy 2>/dev/null | tail -1 > $O/bench_weighted_l2.json
   python -c "import json; r=json.load(open('$O/bench_weighted_l2.json')); print('weighted_l2', r['value'], r['ms_per_step'])"
 fi
 if has fft; then

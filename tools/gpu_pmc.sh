@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 cd /tmp
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout 900 rocprofv3 --pmc $C --kernel-trace -d $O/$C -o pmc --output-format csv -- \
-      python $R/bench.py --steps 2 --warmup 1 --no-graph --no-cpu-baseline --no-roofline "$@" > $O/$C.log 2>&1
+      python $R/bench.py --full --steps 2 --warmup 1 --no-graph --no-cpu-baseline --no-roofline "$@" > $O/$C.log 2>&1
   ls $O/$C | head
 done
 cd $R

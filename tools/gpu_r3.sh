@@ -69,12 +69,12 @@ for r in json.load(open('$O/sweep.json')): print(r['config']['per_gpu_batch'], '
     fullprof)
       cd /tmp
       timeout 900 rocprofv3 --kernel-trace --stats -d $O/fprof -o trace --output-format csv -- \
-          python $R/bench.py --no-cpu-baseline --no-accuracy > $O/fullprof.log 2>&1
+          python $R/bench.py --full --no-cpu-baseline --no-accuracy > $O/fullprof.log 2>&1
       cd $R
       python tools/prof_csv_summary.py $O/fprof 60 > $O/kernel_stats_whole_process.txt 2>&1
       rm -rf $O/fprof
       head -12 $O/kernel_stats_whole_process.txt | cut -c1-150;;
-    full) ( time timeout 900 python bench.py --table $O/table.json ) > $O/bench_full.log 2> $O/bench_full.err; tail -1 $O/bench_full.log | cut -c1-700;;
+    full) ( time timeout 900 python bench.py --full --table $O/table.json ) > $O/bench_full.log 2> $O/bench_full.err; tail -1 $O/bench_full.log | cut -c1-700;;
     probe) ( env $(echo $arg | tr ',' ' ') timeout 300 python tools/parity_probe.py 18 2>>$O/probe.err | tail -1 ) >> $O/probe.jsonl; tail -1 $O/probe.jsonl | cut -c1-900;;
     probe64) ( env $(echo $arg | tr ',' ' ') timeout 300 python tools/parity_probe.py 18 f64 2>>$O/probe.err | tail -1 ) >> $O/probe.jsonl; tail -1 $O/probe.jsonl | cut -c1-900;;
     *) echo "unknown step $step";;

@@ -21,7 +21,7 @@ for step in "$@"; do
            cp gpurun_out/parity_*.json $O/ 2>/dev/null;;
     full) ( time timeout 2400 python -m pytest tests/test_fullsize_models_gpu.py -q ) > $O/full.log 2>&1; grep -E "passed|failed|^FAILED" $O/full.log | cut -c1-250 | tail -4
           cp gpurun_out/parity_whole_model_full_*.json $O/ 2>/dev/null;;
-    bench) ( time timeout 1500 python bench.py --table $O/bench_table.json 2>$O/bench.err | tail -1 ) > $O/bench.json 2>$O/bench.time
+    bench) ( time timeout 1500 python bench.py --full --table $O/bench_table.json 2>$O/bench.err | tail -1 ) > $O/bench.json 2>$O/bench.time
            python -c "import json;r=json.loads(open('$O/bench.json').read().strip().splitlines()[0]);print('bench',r['value'],r['ms_per_step'],'roofline',r['roofline']['kernel'],r['roofline']['avg_launch_us'],r['roofline']['frac'],'cpu',r['cpu_baseline']['value'],'acc',r['accuracy']['hip']['val_rel_l2_mean'],r['accuracy']['welch_t_test'])";;
     quick) ( time timeout 900 python -m pytest tests/test_kernels_gpu.py tests/test_modules_gpu.py -q -k "$arg" ) > $O/quick.log 2>&1; grep -E "passed|failed|^FAILED|^E  " $O/quick.log | cut -c1-250 | tail -12;;
     fetch)
@@ -35,7 +35,7 @@ for step in "$@"; do
     fullprof)
       cd /tmp
       timeout 900 rocprofv3 --kernel-trace --stats -d $O/fprof -o trace --output-format csv -- \
-          python $R/bench.py --no-cpu-baseline --no-accuracy --strong-global-batch 0 $arg > $O/fullprof.log 2>&1
+          python $R/bench.py --full --no-cpu-baseline --no-accuracy --strong-global-batch 0 $arg > $O/fullprof.log 2>&1
       cd $R
       python tools/prof_csv_summary.py $O/fprof 80 > $O/kernel_stats_whole_process.txt 2>&1
       rm -rf $O/fprof
@@ -79,7 +79,7 @@ for r in json.load(open('$O/sweep.json')): print('B', r['config']['per_gpu_batch
     wprof|wpmc|wbench)
       W=${arg%%@*}; BA=""; [[ "$arg" == *@* ]] && BA="--batch ${arg#*@}"
       if [ $name = wbench ]; then
-        timeout 500 python bench.py --workload $W $BA --steps 10 --warmup 3 --no-cpu-baseline --no-accuracy --strong-global-batch 0 --no-f32-leg --table $O/bench_table_$W.json 2>$O/wbench_$W.err | tail -1 > $O/bench_$W.json
+        timeout 500 python bench.py --full --workload $W $BA --steps 10 --warmup 3 --no-cpu-baseline --no-accuracy --strong-global-batch 0 --no-f32-leg --table $O/bench_table_$W.json 2>$O/wbench_$W.err | tail -1 > $O/bench_$W.json
         python -c "import json;r=json.load(open('$O/bench_$W.json'));rf=r.get('roofline') or {};print('$W',r['value'],r['ms_per_step'],r['config']['per_gpu_batch'],rf.get('kernel'),rf.get('avg_launch_us'),rf.get('bound'),rf.get('frac'))"
       elif [ $name = wprof ]; then
         cd /tmp

@@ -9,11 +9,11 @@ cd $R
 export TMPDIR=/tmp
 ( time timeout 900 python -m pytest tests -m gpu -x -q ) > $O/pytest_gpu.log 2>&1
 tail -3 $O/pytest_gpu.log
-( time timeout 900 python bench.py --table $O/table.json "$@" ) > $O/bench.log 2> $O/bench.err
+( time timeout 900 python bench.py --full --table $O/table.json "$@" ) > $O/bench.log 2> $O/bench.err
 tail -1 $O/bench.log
 cd /tmp
 timeout 900 rocprofv3 --kernel-trace --stats -d $O/prof -o trace --output-format csv -- \
-    python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-roofline "$@" > $O/prof.log 2>&1
+    python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-roofline "$@" > $O/prof.log 2>&1
 cd $R
 MS=$(grep '^{"metric' $O/prof.log | tail -1 | python -c "import sys,json; print(json.loads(sys.stdin.read())['ms_per_step']*10)")
 python tools/prof_csv_summary.py $O/prof 60 --last-ms $MS > $O/kernel_stats_steady.txt 2>&1

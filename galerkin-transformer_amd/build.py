@@ -34,24 +34,18 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(emu=False, verbose=False, force=False, tag=None, defines=(), only=None):
-    """tag/defines: extra named variants (ablation builds for tools/ablate_gemm.sh), e.g.
-    build(tag="_nomfma", defines=["GT_ABL_NOMFMA"])."""
+def build(emu=False, verbose=False, force=False):
     os.makedirs(OUT_DIR, exist_ok=True)
-    tag = tag if tag is not None else ("_emu" if emu else "")
+    tag = "_emu" if emu else ""
     objdir = os.path.join(CSRC, ".obj" + tag)
     os.makedirs(objdir, exist_ok=True)
     flags = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I" + INC, "-I" + CSRC]
     if emu:
         flags.append("-DGT_EMULATE_MFMA=1")
-    flags += ["-D" + d for d in defines]
     objs, jobs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
-        if only is not None and src not in only:       # variant builds recompile only the files the define touches
-            objs.append(os.path.join(CSRC, ".obj", src.replace(".hip", ".o")))
-            continue
         if force or _stale(o, [s] + HEADERS):
             jobs.append([_hipcc()] + flags + ["-c", s, "-o", o])
         objs.append(o)
@@ -77,23 +71,8 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--emu", action="store_true")
     ap.add_argument("--force", action="store_true")
-    ap.add_argument("--ablate", action="store_true", help="also build the GEMM ablation variants")
-    ap.add_argument("--ablate-x3", action="store_true", help="also build the split-operand GEMM ablation variants")
-    ap.add_argument("--ablate-head", action="store_true", help="also build the head_bwd16_kernel timing ablations")
     ap.add_argument("-v", "--verbose", action="store_true")
     a = ap.parse_args()
     print(build(False, a.verbose, a.force))
     if a.emu:
         print(build(True, a.verbose, a.force))
-    if a.ablate_x3:
-        for t, d in (("_x3nomfma", ["GT_ABL_X3_NOMFMA"]), ("_x3nosplit", ["GT_ABL_X3_NOSPLIT_A", "GT_ABL_X3_NOSPLIT_B"]),
-                     ("_x3nosplitb", ["GT_ABL_X3_NOSPLIT_B"]), ("_x3nostore", ["GT_ABL_X3_NOSTORE"]),
-                     ("_x3onlyload", ["GT_ABL_X3_NOMFMA", "GT_ABL_X3_NOSPLIT_A", "GT_ABL_X3_NOSPLIT_B", "GT_ABL_X3_NOSTORE"])):
-            print(build(False, a.verbose, a.force, tag=t, defines=d, only=["gt_gemm_x3.hip"]))
-    if a.ablate_head:
-        for m in (1, 2, 3, 4, 8, 16, 31):
-            print(build(False, a.verbose, a.force, tag=f"_h16abl{m}", defines=[f"H16_ABL={m}"], only=["gt_head.hip"]))
-    if a.ablate:
-        for t, d in (("_nomfma", ["GT_ABL_NOMFMA"]), ("_noload", ["GT_ABL_NOLOAD"]),
-                     ("_nostore", ["GT_ABL_NOSTORE"]), ("_onlymfma", ["GT_ABL_NOLOAD", "GT_ABL_NOSTORE"])):
-            print(build(False, a.verbose, a.force, tag=t, defines=d))

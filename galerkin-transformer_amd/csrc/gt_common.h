@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include "gt_hip.h"
 
 namespace gt {
@@ -149,5 +150,22 @@ int tsmm_run(const gt_gemm_desc* d, void* ws, int64_t ws_bytes, void* stream);
         hipError_t e__ = hipGetLastError();       \
         if (e__ != hipSuccess) return (int)e__;   \
     } while (0)
+
+// A kernel launched with more than 64 KiB of dynamic LDS has to opt in first.  The attribute is per device: one bit per
+// device ordinal and kernel instance, set once (concurrent host threads at worst set it twice).  0, or GT_ENOTSUP if the
+// runtime refuses `bytes`.
+template <auto Kern>
+int gt_allow_dynamic_lds(size_t bytes) {
+    static std::atomic<uint64_t> done{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const uint64_t bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_acquire) & bit) return 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) !=
+        hipSuccess)
+        return GT_ENOTSUP;
+    done.fetch_or(bit, std::memory_order_release);
+    return 0;
+}
 
 }  // namespace gt

@@ -25,7 +25,7 @@
 //    free: their VALU work interleaves there (one loader wave alone sustained ~6.5 clk per instruction and, holding a whole
 //    row pair in registers, spilled to scratch: 204 us for the 48-channel launch against 144 us of matrix time; staged by the
 //    MFMA waves themselves 307 us; four loader waves sharing the MFMA waves' SIMDs 280 us).
-//  * Sign-alternating accumulation (gt_gemm_x3.hip: GT_X3_ALT): channels at odd LDS positions enter negated on both sides,
+//  * Sign-alternating accumulation (as in gt_gemm_x3.hip): channels at odd LDS positions enter negated on both sides,
 //    the accumulators are un-flipped when the block writes its partial result.
 //
 //  * Two arithmetics (template parameter F16): the three bf16 planes / six products of GT_PREC_BF16X3, or the two fp16 planes /
@@ -39,11 +39,9 @@
 // Partial results go to slabs [image, row chunk][tap][ci][co] and are summed in a fixed order by convw_reduce_kernel, which
 // also transposes to the reference's [co][ci][3][3] and applies alpha: deterministic, no atomics.
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 #include "gt_common.h"
-#include <atomic>
 
 namespace gt {
 
@@ -55,9 +53,6 @@ typedef uint32_t cw_u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) f32x4 cw_gf32x4;
 typedef __attribute__((address_space(1))) float cw_gf32;
 
-#ifndef GT_CW_ABL
-#define GT_CW_ABL 0
-#endif
 constexpr int CW_LOADERS = 64;          // threads of one loader wave
 constexpr int CW_THREADS = 320;         // wave 0: the x loader, waves 1..3: dy = -1, 0, 1 (MFMA), wave 4: the gy loader
 constexpr int CW_NQ = 10;              // pixel groups (units) per row and channel: 80 pixels
@@ -231,11 +226,7 @@ __device__ __noinline__ void cw_loader(const float* base, int64_t ld, int H, int
             scale = cw_pow2(e);
             if (lt == 0) exps[slot] = e;
         }
-#if GT_CW_ABL != 1            // ablation build 1 (timing only): the loaders fetch but neither split nor write
         st.store(buf + slot * (ROLE == 0 ? G::XSLOT : G::YBUF), scale);
-#else
-        if (scale == 12345.f) st.store(buf + slot * (ROLE == 0 ? G::XSLOT : G::YBUF), scale);
-#endif
     };
     if (ROLE == 0) {
         for (int r = -1; r <= 1; ++r) {
@@ -351,11 +342,9 @@ __device__ __noinline__ void cw_mfma(float* slab, int Cin, int Cout, int ci0, in
                 eacc = es;
             }
         }
-#if GT_CW_ABL != 2            // ablation build 2 (timing only): the MFMA waves only keep the barriers
         kstep(xr, yr, kq, std::false_type{});
         kstep(xr, yr, 4 + kq, std::false_type{});
         kstep(xr, yr, 8 + kq, std::true_type{});
-#endif
         __syncthreads();                                   // row y is done with; the loader has published rows y + 2 / y + 1
     }
 
@@ -440,10 +429,6 @@ static bool cw_plan(int B, int H, int W, int Cin, int Cout, int f16, CwPlan* pl)
     } else {
         return false;
     }
-    if (const char* e = getenv("GT_CW_CIT")) {              // tuning override (tools): input-channel tiles per block
-        const int c = atoi(e);
-        if (c >= 1 && c <= 4 && Cin % (16 * c) == 0 && (c < 4 || f16) && !(pl->cot == 4 && c != 2 && c != 4)) pl->cit = c;
-    }
     pl->ciblocks = Cin / (16 * pl->cit);
     pl->coblocks = Cout / (16 * pl->cot);
     const int per_row = B * pl->ciblocks * pl->coblocks * pl->nseg;
@@ -454,6 +439,14 @@ static bool cw_plan(int B, int H, int W, int Cin, int Cout, int f16, CwPlan* pl)
     const size_t planes = f16 ? 2 : 3;
     pl->lds = 4 * planes * CW_NQ * 16 * pl->cit * 16 + 2 * planes * (CW_NQ + 2) * 16 * pl->cot * 16 + 16 + 32;
     return true;
+}
+
+// more than 64 KB of LDS per block: the limit is raised once per device and kernel instance
+template <auto Kern>
+static int cw_launch(const CwPlan& pl, dim3 grid, const ConvWP& p, hipStream_t st) {
+    if (int rc = gt_allow_dynamic_lds<Kern>(pl.lds)) return rc;
+    hipLaunchKernelGGL(Kern, grid, dim3(CW_THREADS), pl.lds, st, p);
+    return 0;
 }
 
 }  // namespace gt
@@ -485,36 +478,20 @@ extern "C" int gt_conv3x3_wgrad_nhwc(const float* gy, int64_t ldg, const float* 
     ConvWP p{gy, ldg, x, ldx, reinterpret_cast<float*>(ws), B, H, W, Cin, Cout, pl.chunks, pl.rows, pl.nseg, pl.seg_w};
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)nslab, (unsigned)pl.ciblocks, (unsigned)pl.coblocks);
-    // more than 64 KB of LDS per block: the limit is raised once per kernel instance
-    // (the attribute is per device: one bit per device ordinal, set once; concurrent host threads at worst set it twice)
-    static std::atomic<uint64_t> raised[16];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t dbit = 1ull << (dev & 63);
-    auto launch = [&](auto kern, int idx) -> int {
-        if (!(raised[idx].load(std::memory_order_acquire) & dbit)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)pl.lds) != hipSuccess)
-                return GT_ENOTSUP;
-            raised[idx].fetch_or(dbit, std::memory_order_release);
-        }
-        hipLaunchKernelGGL(kern, grid, dim3(CW_THREADS), pl.lds, st, p);
-        return 0;
-    };
     int rc = GT_ENOTSUP;
     const int key = pl.f16 * 100 + pl.cit * 10 + pl.cot;
     switch (key) {
-        case 13: rc = launch(convw_kernel<1, 3, 0>, 0); break;
-        case 23: rc = launch(convw_kernel<2, 3, 0>, 1); break;
-        case 33: rc = launch(convw_kernel<3, 3, 0>, 2); break;
-        case 24: rc = launch(convw_kernel<2, 4, 0>, 3); break;
-        case 113: rc = launch(convw_kernel<1, 3, 1>, 4); break;
-        case 123: rc = launch(convw_kernel<2, 3, 1>, 5); break;
-        case 133: rc = launch(convw_kernel<3, 3, 1>, 6); break;
-        case 143: rc = launch(convw_kernel<4, 3, 1>, 7); break;
-        case 124: rc = launch(convw_kernel<2, 4, 1>, 8); break;
-        case 144: rc = launch(convw_kernel<4, 4, 1>, 9); break;
-        case 142: rc = launch(convw_kernel<4, 2, 1>, 10); break;
+        case 13: rc = cw_launch<convw_kernel<1, 3, 0>>(pl, grid, p, st); break;
+        case 23: rc = cw_launch<convw_kernel<2, 3, 0>>(pl, grid, p, st); break;
+        case 33: rc = cw_launch<convw_kernel<3, 3, 0>>(pl, grid, p, st); break;
+        case 24: rc = cw_launch<convw_kernel<2, 4, 0>>(pl, grid, p, st); break;
+        case 113: rc = cw_launch<convw_kernel<1, 3, 1>>(pl, grid, p, st); break;
+        case 123: rc = cw_launch<convw_kernel<2, 3, 1>>(pl, grid, p, st); break;
+        case 133: rc = cw_launch<convw_kernel<3, 3, 1>>(pl, grid, p, st); break;
+        case 143: rc = cw_launch<convw_kernel<4, 3, 1>>(pl, grid, p, st); break;
+        case 124: rc = cw_launch<convw_kernel<2, 4, 1>>(pl, grid, p, st); break;
+        case 144: rc = cw_launch<convw_kernel<4, 4, 1>>(pl, grid, p, st); break;
+        case 142: rc = cw_launch<convw_kernel<4, 2, 1>>(pl, grid, p, st); break;
         default: break;
     }
     if (rc) return rc;

@@ -552,7 +552,6 @@ static void fourier16_launch_nw(const F16P& p, bool dual, bool block16, hipStrea
 // Measured at C3's layer shape (B = 8, n = 3721; tests/test_fourier16_gpu.py -k time): forward 0.247 ms with 8 waves per block
 // vs 0.271 with 4; the dual pass (2 waves per SIMD) 0.586 vs 0.546 -- it keeps 4.
 static int f16_pick_nw(int64_t BH, int ntile, bool dual) {
-    if (const char* e = getenv("GT_F16_NW")) { const int v = atoi(e); if (v == 4 || v == 8) return v; }
     return (!dual && ntile >= 16 && BH * ((ntile + 7) / 8) >= 384) ? 8 : 4;
 }
 

@@ -116,12 +116,10 @@ __global__ __launch_bounds__(WM* WN * 64, ((HEAD == 0 && BK == 16) ? 4 : 1)) voi
     __syncthreads();
     for (int kt = 0; kt < nk; ++kt) {
         const int buf = kt & 1;
-#ifndef GT_ABL_NOLOAD
         if (kt + 1 < nk) {
             if (kt + 1 == nk1) enter_seg2();
             g2r(kt + 1 < nk1 ? kbeg + (kt + 1) * BK : (kt + 1 - nk1) * BK);
         }
-#endif
         const float* __restrict__ cA = sA + buf * BK * BM;
         const float* __restrict__ cB = sB + buf * BK * BN;
 #pragma unroll
@@ -306,10 +304,8 @@ __global__ __launch_bounds__(256, (MT == 4 ? 2 : 3)) void gemm_stream_kernel(con
             } else {
                 asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
             }
-#ifndef GT_ABL_NOLOAD
             if (kt + 1 < cur.nk) issue(cur, cur.kbeg + (kt + 1) * BK, (g + 1) & 1);
             else if (have_next) issue(nxt, nxt.kbeg, (g + 1) & 1);
-#endif
             const float* __restrict__ cA = smem + (g & 1) * STAGE;
             const float* __restrict__ cB = cA + SA;
             const int kbase = cur.kbeg + kt * BK;

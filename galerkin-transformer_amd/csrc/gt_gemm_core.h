@@ -122,10 +122,6 @@ __device__ __forceinline__ void lds_frag(const float* __restrict__ s, float (&f)
 }
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-#ifdef GT_ABL_NOMFMA      // ablation build (tools/ablate_gemm.sh): keep the operands live, skip the matrix pipe
-    asm volatile("" ::"v"(a), "v"(b));
-    return c;
-#endif
 #ifdef GT_EMULATE_MFMA
     // Debug build: the same distributed-operand semantics with shuffles (documents the layout the
     // kernel assumes: A[row=lane&15][k=lane>>4], B[k=lane>>4][col=lane&15], D[row=4*(lane>>4)+r][col=lane&15]).
@@ -285,9 +281,6 @@ template <int MT, int NT>
 __device__ __forceinline__ void gemm_epilogue(const GemmP& p, const f32x4 (&acc)[MT][NT], int mw0, int nb,
                                               int z, int b0, int b1, int sidx, int kq) {
     if (nb >= p.N) return;
-#ifdef GT_ABL_NOSTORE
-    if (acc[0][0][0] != 12345.678f) return;
-#endif
     const bool full = (nb + NT <= p.N);
     const int64_t coff = b0 * p.c_bs0 + b1 * p.c_bs1 + (int64_t)sidx * p.c_split;
     float* __restrict__ C = p.C + coff;

@@ -103,14 +103,10 @@ __device__ __forceinline__ void x3_store8(char* __restrict__ img, int row, int k
 }
 
 __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
-#ifdef GT_ABL_X3_NOMFMA          // ablation build: keep the operands live, skip the matrix pipe
-    asm volatile("" ::"v"(a), "v"(b));
-    return c;
-#endif
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
-// Sign-alternating accumulation (GT_X3_ALT, default on).  Measured on gfx950 (tools/mfma_chain_probe.hip,
+// Sign-alternating accumulation.  Measured on gfx950 (tools/mfma_chain_probe.hip,
 // profiles/r05_mfma_chain_probe.json): the bf16 MFMA does not round its sum to nearest -- addends whose low bits fall below
 // the accumulator's guard bits are chopped toward -infinity.  Per instruction that is ~2^-9 ulp, but it has ONE direction:
 // a chain of six plane products per stage ends ~0.1 of its rms error below the exact sum in EVERY output element, whatever
@@ -122,22 +118,17 @@ __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
 // has no register left for a per-lane sign, alternates its M side per 32-row tile instead), so the chain of output
 // (m, n) is accumulated with the sign (-1)^(m+n), and undo it on the accumulator before the epilogue: per-element
 // accuracy is unchanged, the offset alternates in a checkerboard and cancels in any sum over rows or columns.
-#ifndef GT_X3_ALT
-#define GT_X3_ALT 1
-#endif
 // sign of operand row `parity & 1`
-__device__ __forceinline__ float x3_alt_sign(int parity) { return (GT_X3_ALT && (parity & 1)) ? -1.f : 1.f; }
+__device__ __forceinline__ float x3_alt_sign(int parity) { return (parity & 1) ? -1.f : 1.f; }
 // accumulator register e of a lane = output (m = the lane's own row, n = .. + 8 (e >> 2) + 4 lh + (e & 3)): n's parity is e & 1
 template <int NI, int NJ>
 __device__ __forceinline__ void x3_alt_undo(f32x16 (&acc)[NI][NJ], float rsgn) {
-#if GT_X3_ALT
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] *= (e & 1) ? -rsgn : rsgn;
-#endif
 }
 
 // ---- two-term fp16 arithmetic (GT_PREC_F16X2) --------------------------------------------------------------------------
@@ -154,12 +145,8 @@ __device__ __forceinline__ void x3_alt_undo(f32x16 (&acc)[NI][NJ], float rsgn) {
 //     multiplied by the same power of two (exact) -- the online-rescaling of a streaming softmax, applied to a dot
 //     product.  Nothing can overflow (the check precedes the split), a row whose early stages are its largest simply
 //     resolves the later ones relative to that maximum, like any fp32 accumulation does.
-// The accumulators are un-scaled together with the GT_X3_ALT sign, before the epilogue.
-#ifndef GT_X3H_CVT_SPLIT
-#define GT_X3H_CVT_SPLIT 0      // 1: the round-4 split (multiply, v_cvt_pk, two v_cvt, subtract, v_cvt_pk) for A/B timing
-#endif
+// The accumulators are un-scaled together with the alternating sign, before the epilogue.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 constexpr int X3H_E0 = 120;                       // start exponent: any non-zero first stage sets the real one
 constexpr int X3H_TARGET = 13, X3H_LIMIT = 15;    // scaled row amax is put in [2^13, 2^14) and kept below 2^15
 
@@ -167,15 +154,7 @@ __device__ __forceinline__ float x3h_pow2(int e) { return __uint_as_float((uint3
 
 // two fp32 times the scale -> two packed fp16 pairs (round 5: four v_fma_mix* instead of multiply + conversions, gt_common.h)
 __device__ __forceinline__ void x3h_split_pair(float a, float b, float s, uint32_t (&out)[2]) {
-#if GT_X3H_CVT_SPLIT
-    const f32x2 r = f32x2{a, b} * s;
-    const f16x2 h0 = __builtin_convertvector(r, f16x2);           // v_cvt_pk_f16_f32 (RNE)
-    const f16x2 h1 = __builtin_convertvector(r - __builtin_convertvector(h0, f32x2), f16x2);
-    out[0] = __builtin_bit_cast(uint32_t, h0);
-    out[1] = __builtin_bit_cast(uint32_t, h1);
-#else
     f16_mulsplit_pair(a, s, b, s, out[0], out[1]);
-#endif
 }
 
 __device__ __forceinline__ f32x16 mfma32h(f16x8 a, f16x8 b, f32x16 c) {
@@ -191,9 +170,6 @@ __device__ __forceinline__ f32x16 mfma32h(f16x8 a, f16x8 b, f32x16 c) {
 // r02m_pmc_step_summary.txt).  The wave therefore transposes its 32 x 64 row tile through a private LDS tile first:
 // afterwards 16 consecutive lanes hold one row's 64 columns and every global access of the fused epilogue is a full
 // 256-byte row segment.  mtile0 / ntile0: first row / column of the wave's tile.  stg: 32 x X3_EP_SW floats.
-#ifndef GT_X3_EP_FAST                              // 0: every tile through ep_row (the round-2 epilogue), for A/B timing
-#define GT_X3_EP_FAST 1
-#endif
 constexpr int X3_EP_SW = 68;                     // staging row pitch in floats (64 + 4: conflict-free both ways)
 constexpr int X3_EP_STG = 32 * X3_EP_SW;
 
@@ -209,7 +185,7 @@ __device__ __forceinline__ void x3_bias4(const GemmP& p, int ntile0, int lane, f
 // one row segment at a time behind run-time switches: each segment's res / aux load was followed by its use, and the
 // s_waitcnt vmcnt(0) in front of that use also waited for the STORES of the segments before it -- sixteen store round
 // trips in a row per wave.  A block of the FFN launch spent 15.6 us of its 28.7 us in the epilogue writing 64 KB, and
-// 55-60 % of the resident blocks of the chip were in that state at any time (tools/x3p_prof.py, profiles/r03z_*).
+// 55-60 % of the resident blocks of the chip were in that state at any time (per-block wall-clock stamps, profiles/r03z_*).
 // Here a wave works in batches of four segments (16 rows x 256 B): the res / aux loads of batch b + 1 are issued before
 // the stores of batch b, the values of a batch are computed together, and nothing ever waits for a store.
 template <int MI>
@@ -376,12 +352,10 @@ __device__ __forceinline__ void x3_epilogue(const GemmP& p, const f32x16 (&acc)[
     float biasv[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) biasv[t] = bias_pre ? bias_pre[t] : (p.bias && nb + t < p.N) ? p.bias[nb + t] : 0.f;
-#if GT_X3_EP_FAST
     if (p.c_vec && !p.raw && !p.rp && !p.add && ntile0 + 64 <= p.N && mtile0 + 32 * MI <= p.M) {   // wave-uniform
         x3_epilogue_fast<MI>(p, acc, mtile0, nb, lane, stg, C, z, b0, b1, biasv, dkey);
         return;
     }
-#endif
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
 #pragma unroll
@@ -610,7 +584,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(const GemmP p) {
     auto r2s = [&](int buf) {                     // first use of the loaded registers: the vmcnt wait lands here
         if (p.a_drop.thresh) x3_mask8<LA>(p.a_drop, akey, p.a_drop_ld, adoff, m0 + arow, ka, ra);
         if (LA == 1 && do_acs) asum += ((ra[0] + ra[1]) + (ra[2] + ra[3])) + ((ra[4] + ra[5]) + (ra[6] + ra[7]));
-        if (GT_X3_ALT) {                          // odd operand rows enter negated (tile origins are even)
+        {                                         // odd operand rows enter negated (tile origins are even)
             const float sa_ = x3_alt_sign(arow), sb_ = x3_alt_sign(brow);
 #pragma unroll
             for (int j = 0; j < 8; ++j) { ra[j] *= sa_; rb[j] *= sb_; }
@@ -921,29 +895,17 @@ __global__ __launch_bounds__(256, (R <= 3 ? 3 : 2)) void gemm_x3r_kernel(const G
             x3r_frag<LA>(sa, row, lh, v);
             if (p.a_drop.thresh) x3_mask8<LA>(p.a_drop, akey, p.a_drop_ld, adoff, m0 + row, kbase, v);
             if (LA == 1 && do_acs) asum[i] += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-            if (GT_X3_ALT) {                      // row parity = lane parity on both sides (see x3_alt_undo)
 #pragma unroll
-                for (int q = 0; q < 8; ++q) v[q] *= rsgn;
-            }
-#ifdef GT_ABL_X3_NOSPLIT_A       // ablation builds (tools/ablate_x3.sh): timing only, results are wrong
-            for (int pl = 0; pl < PLANES; ++pl) am[i][pl] = __builtin_bit_cast(bf16x8, u32x4{__float_as_uint(v[0]), __float_as_uint(v[2]), __float_as_uint(v[4]), __float_as_uint(v[6])});
-#else
+            for (int q = 0; q < 8; ++q) v[q] *= rsgn;     // row parity = lane parity on both sides (see x3_alt_undo)
             x3r_split<PLANES>(v, am[i]);
-#endif
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             float v[8];
             x3r_frag<LB>(sb, wn * 64 + 32 * j + lr, lh, v);
-            if (GT_X3_ALT) {
 #pragma unroll
-                for (int q = 0; q < 8; ++q) v[q] *= rsgn;
-            }
-#ifdef GT_ABL_X3_NOSPLIT_B
-            for (int pl = 0; pl < PLANES; ++pl) bn[j][pl] = __builtin_bit_cast(bf16x8, u32x4{__float_as_uint(v[1]), __float_as_uint(v[3]), __float_as_uint(v[5]), __float_as_uint(v[7])});
-#else
+            for (int q = 0; q < 8; ++q) v[q] *= rsgn;
             x3r_split<PLANES>(v, bn[j]);
-#endif
         }
 #pragma unroll
         for (int s = PLANES - 1; s >= 0; --s) {          // plane pairs (pa, pb) with pa + pb = s <= PLANES - 1
@@ -958,9 +920,6 @@ __global__ __launch_bounds__(256, (R <= 3 ? 3 : 2)) void gemm_x3r_kernel(const G
             }
         }
     }
-#ifdef GT_ABL_X3_NOSTORE
-    if (acc[0][0][0] != 12345.678f) return;
-#endif
 
     if (LA == 1 && do_acs) {        // row sums of the (masked) A operand: combine the two k-halves of a row
 #pragma unroll
@@ -984,7 +943,7 @@ __global__ __launch_bounds__(256, (R <= 3 ? 3 : 2)) void gemm_x3r_kernel(const G
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Packed-B variant: when B is small next to A (a weight matrix against many token rows), every block would split the
-// same B values again -- the in-situ ablation put the B split alone at 2.5 of 37.5 ms/step (tools/ablate_x3.sh).
+// same B values again -- an in-situ ablation put the B split alone at 2.5 of 37.5 ms/step.
 // x3_pack_b_kernel splits B ONCE into its three bf16 planes, stored in MFMA fragment order
 //     Bp[plane][n-tile of 32][k-stage of 16][lane 0..63] = 8 bf16  (k = 16 ks + 8 (lane >> 5) + e, n = 32 nt + (lane & 31)),
 // zero beyond N and K, n-tiles padded to whole 128-column block tiles.  A wave then reads a B fragment of a stage as ONE
@@ -992,11 +951,7 @@ __global__ __launch_bounds__(256, (R <= 3 ? 3 : 2)) void gemm_x3r_kernel(const G
 // per weight), B needs no LDS, and the ring holds A only (8 KB per stage, depth 4).  The fragments of stage kt + 1 are
 // requested at the top of iteration kt into a second register set; the counted waits (vector-memory loads retire in
 // order) are written out next to the loop.
-#ifndef GT_X3P_RING                                // A-ring depth of the packed-B kernel (stages of 8 KB)
-#define GT_X3P_RING 4
-#endif
-constexpr int X3P_R = GT_X3P_RING;
-static_assert(X3P_R >= 3 && X3P_R <= 6, "the counted waits below are written out for ring depths 3..6");
+constexpr int X3P_R = 4;                          // A-ring depth of the packed-B kernel (stages of 8 KB)
 
 // Row of the weight behind tile row n (pad48: the tile rows are 64-column head slots holding 48-wide heads, the 16 rows behind
 // a head are zero -- gt_gemm.hip: hn_slots; N counts slot rows then), -1: a zero row.
@@ -1019,7 +974,7 @@ __global__ __launch_bounds__(256) void x3_pack_b_kernel(const float* __restrict_
     for (int e = 0; e < 8; ++e) {
         const int k = k0 + e;
         v[e] = (nr >= 0 && k < K) ? (layout_b == 0 ? B[(int64_t)nr * ldb + k] : B[(int64_t)k * ldb + nr]) : 0.f;
-        v[e] *= x3_alt_sign(n);                    // GT_X3_ALT: odd rows of the N-side operand enter negated
+        v[e] *= x3_alt_sign(n);                    // odd rows of the N-side operand enter negated
     }
     uint32_t q[4][3];
 #pragma unroll
@@ -1074,7 +1029,7 @@ __device__ __forceinline__ void x3_pack_b16_tile(const float* __restrict__ B, in
     for (int i = 0; i < 16; ++i) amax = fmaxf(amax, red[i]);
     const int ex = (int)((__float_as_uint(amax) >> 23) & 0xff);
     const int e = ex == 0 ? 0 : X3H_TARGET + 127 - ex;            // amax 2^e in [2^13, 2^14); an all-zero tile keeps 1
-    const float sc = x3h_pow2(e) * x3_alt_sign(n);                // GT_X3_ALT: odd rows of the N-side operand enter negated
+    const float sc = x3h_pow2(e) * x3_alt_sign(n);                // odd rows of the N-side operand enter negated
     auto store = [&](int ks, const float (&v)[8]) {
         uint32_t q[4][2];
 #pragma unroll
@@ -1117,23 +1072,11 @@ __global__ __launch_bounds__(1024) void x3_pack_b16_many_kernel(const PackManyP 
                      p.pad48[e]);
 }
 
-#ifndef GT_X3P_BLOCKS                              // resident blocks per CU the general instances are compiled for
-#define GT_X3P_BLOCKS 3
-#endif
-#ifdef GT_X3P_PROF                                 // tools/x3p_prof.py: wall-clock stamps (100 MHz) of every block's phases
-__device__ unsigned long long x3p_prof[8 * 8192];
-extern "C" int gt_debug_x3p_prof(void* dst, long long bytes) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(x3p_prof), (size_t)bytes);
-}
-#define X3P_STAMP(i) const unsigned long long ts##i = __builtin_amdgcn_s_memrealtime()
-#else
-#define X3P_STAMP(i)
-#endif
 // BN = 128: 2 x 2 waves of 64 x 64;  BN = 64 (narrow outputs: the 42 / 44-channel convolutions of the down-scaler, padded to
 // 48): 4 x 1 waves of 32 x 64 -- a wave then splits ONE 32-row tile of A per stage for its twelve MFMAs, the same split-to-
 // matrix ratio as the wide tile, and a 48-column product wastes a quarter of the tile instead of five eighths.
 template <int LA, int HN, int CV, int BN = 128>     // CV: 0 plain, 1 implicit 3x3 convolution on A
-__global__ __launch_bounds__(256, ((HN > 0 || LA == 1 || CV == 1) ? 3 : GT_X3P_BLOCKS)) void gemm_x3p_kernel(const GemmP p) {
+__global__ __launch_bounds__(256, 3) void gemm_x3p_kernel(const GemmP p) {
     constexpr int MI = BN == 64 ? 1 : 2;           // 32-row tiles of A per wave
     static_assert(BN == 128 || (BN == 64 && HN == 0 && LA == 0), "the narrow tile serves plain / convolution launches");
     constexpr int R = X3P_R, PLANES = 3;
@@ -1141,7 +1084,6 @@ __global__ __launch_bounds__(256, ((HN > 0 || LA == 1 || CV == 1) ? 3 : GT_X3P_B
     constexpr int SMEM = R * X3R_OP > STG ? R * X3R_OP : STG;
     __shared__ __attribute__((aligned(16))) char smem[SMEM];
 
-    X3P_STAMP(0);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = BN == 64 ? wave : wave >> 1, wn = BN == 64 ? 0 : wave & 1;
     const int wrow = BN == 64 ? wm * 32 : wm * 64; // first tile row of this wave
@@ -1169,7 +1111,7 @@ __global__ __launch_bounds__(256, ((HN > 0 || LA == 1 || CV == 1) ? 3 : GT_X3P_B
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
     const int nk = (kend + X3_BK - 1) / X3_BK;
-    // GT_X3_ALT in this kernel (no register to spare for a per-lane sign): the M-side sign alternates per 32-ROW TILE -- a
+    // Sign alternation in this kernel (no register to spare for a per-lane sign): the M-side sign alternates per 32-ROW TILE -- a
     // compile-time constant of the unrolled tile loop for the 64-row wave tile (a source modifier of the split's first
     // instructions), the wave's parity (a scalar) for the 32-row one -- the N-side per column (x3_pack_b_kernel)
     const float tsgn = x3_alt_sign(BN == 64 ? __builtin_amdgcn_readfirstlane(wm) : 0);
@@ -1216,21 +1158,14 @@ __global__ __launch_bounds__(256, ((HN > 0 || LA == 1 || CV == 1) ? 3 : GT_X3P_B
     // iteration, and is consumed one iteration later.  Vector-memory loads retire in order, so a wait for B also waits for
     // every A stage requested before it: with ONE set the loads of B(kt + 1) can only go out behind the MFMAs of B(kt), and
     // their latency (plus that of the A stage requested one iteration earlier) stands in front of every stage's MFMAs --
-    // load, matrix and store time of a launch add up instead of overlapping (tools/ablate_x3.sh: 37 + 15 + 30 = 82 us).
+    // load, matrix and store time of a launch add up instead of overlapping (timing ablations: 37 + 15 + 30 = 82 us).
     bf16x8 bn0[2][PLANES], bn1[2][PLANES];
     auto loadb = [&](int ks, bf16x8 (&bn)[2][PLANES]) {
-#ifdef GT_ABL_X3_NOLOADB         // ablation: the B fragments are fetched for the first two stages only (timing; wrong results)
-        if (ks > 1) return;
-#endif
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int pl = 0; pl < PLANES; ++pl) {
-#ifdef GT_ABL_X3_NOSPLIT_B       // ablation: every stage reads the same (cache-resident) fragment
-                const char* sp = bbase + pl * bplane + (int64_t)j * p.bp_KS * 1024;
-#else
                 const char* sp = bbase + pl * bplane + ((int64_t)j * p.bp_KS + ks) * 1024;
-#endif
                 asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(bn[j][pl]) : "v"(voff), "s"(sp));
             }
     };
@@ -1246,15 +1181,11 @@ __global__ __launch_bounds__(256, ((HN > 0 || LA == 1 || CV == 1) ? 3 : GT_X3P_B
             const int row = wrow + 32 * i + lr;
             x3r_frag<LA>(sa, row, lh, v);
             if (p.a_drop.thresh) x3_mask8<LA>(p.a_drop, akey, p.a_drop_ld, 0, m0 + row, kbase, v);
-            if (GT_X3_ALT && (MI == 1 || (i & 1))) {   // M-side: the sign alternates per 32-row tile (see below)
+            if (MI == 1 || (i & 1)) {             // M-side: the sign alternates per 32-row tile (see below)
 #pragma unroll
                 for (int q = 0; q < 8; ++q) v[q] = MI == 1 ? v[q] * tsgn : -v[q];
             }
-#ifdef GT_ABL_X3_NOSPLIT_A       // ablation builds (tools/ablate_x3.sh): timing only, results are wrong
-            for (int pl = 0; pl < PLANES; ++pl) am[pl] = __builtin_bit_cast(bf16x8, u32x4{__float_as_uint(v[0]), __float_as_uint(v[2]), __float_as_uint(v[4]), __float_as_uint(v[6])});
-#else
             x3r_split<PLANES>(v, am);
-#endif
 #pragma unroll
             for (int s = PLANES - 1; s >= 0; --s) {      // plane pairs (pa, pb) with pa + pb = s, smallest terms first
 #pragma unroll
@@ -1274,31 +1205,16 @@ __global__ __launch_bounds__(256, ((HN > 0 || LA == 1 || CV == 1) ? 3 : GT_X3P_B
     // the end of K the A loader reads the zero line into a free slot and B re-reads its last stage -- so the counts hold
     // to the last stage and no load sits under a branch: a conditional asm load makes hipcc allocate fresh registers for
     // it and COPY them into the set at the join, before the data has arrived (seen in the ISA of a first version).
-#define X3P_WAIT_AB_(N, bn)                                                                                            \
+#define X3P_WAIT_AB(N, bn)                                                                                             \
     asm volatile("s_waitcnt vmcnt(" #N ")\n\ts_barrier"                                                                \
                  : "+v"(bn[0][0]), "+v"(bn[0][1]), "+v"(bn[0][2]), "+v"(bn[1][0]), "+v"(bn[1][1]), "+v"(bn[1][2])      \
                  :                                                                                                     \
                  : "memory")
-#ifdef GT_X3P_PROF                                 // time spent in the waits of the K loop (wave 0)
-    unsigned long long tw_sum = 0;
-#define X3P_WAIT_AB(N, bn)                                                                                             \
-    do {                                                                                                               \
-        const unsigned long long w0_ = __builtin_amdgcn_s_memrealtime();                                              \
-        X3P_WAIT_AB_(N, bn);                                                                                           \
-        tw_sum += __builtin_amdgcn_s_memrealtime() - w0_;                                                              \
-    } while (0)
-#else
-#define X3P_WAIT_AB(N, bn) X3P_WAIT_AB_(N, bn)
-#endif
     const int klast = nk - 1;
     loadb(0, bn0);
 #pragma unroll
     for (int s = 0; s < R - 1; ++s) issue(s);
-    if (R == 3) X3P_WAIT_AB(2, bn0);               // iteration 0: behind A(0) are the R - 2 other stages of the prologue
-    else if (R == 4) X3P_WAIT_AB(4, bn0);
-    else if (R == 5) X3P_WAIT_AB(6, bn0);
-    else X3P_WAIT_AB(8, bn0);
-    X3P_STAMP(1);
+    X3P_WAIT_AB(4, bn0);                           // iteration 0: behind A(0) are the R - 2 other stages of the prologue
     loadb(klast < 1 ? klast : 1, bn1);
     issue(R - 1);
     stage(0, bn0);
@@ -1317,15 +1233,9 @@ __global__ __launch_bounds__(256, ((HN > 0 || LA == 1 || CV == 1) ? 3 : GT_X3P_B
         X3P_WAIT_AB(2, bn1);
         stage(kt, bn1);
     }
-    X3P_STAMP(2);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the zero stages requested past the end of K: the ring becomes staging
 #undef X3P_WAIT_AB
-#undef X3P_WAIT_AB_
-#ifdef GT_ABL_X3_NOSTORE
-    if (acc[0][0][0] != 12345.678f) return;
-#endif
 
-#if GT_X3_ALT
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -1335,7 +1245,6 @@ __global__ __launch_bounds__(256, ((HN > 0 || LA == 1 || CV == 1) ? 3 : GT_X3P_B
                 const float sg = MI == 1 ? tsgn : ((i & 1) ? -1.f : 1.f);
                 acc[i][j][e] *= (e & 1) ? -sg : sg;
             }
-#endif
     __syncthreads();                               // every wave is done with the ring: its first slots become staging
     if constexpr (HN > 0)
         x3_epilogue_hn<(HN > 0 ? HN : 32), 2>(p, acc, m0 + wm * 64 + lr, n0 + wn * 64 + 4 * lh, lane,
@@ -1343,18 +1252,6 @@ __global__ __launch_bounds__(256, ((HN > 0 || LA == 1 || CV == 1) ? 3 : GT_X3P_B
     else
         x3_epilogue<MI>(p, acc, m0 + wrow, n0 + wn * 64, lane, reinterpret_cast<float*>(smem) + wave * X3_EP_STG, 0, 0, 0, 0,
                         bias4);
-#ifdef GT_X3P_PROF
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the block's stores have left
-    X3P_STAMP(3);
-    if (tid == 0 && blockIdx.x < 8192) {
-        unsigned long long* o = x3p_prof + 8 * blockIdx.x;
-        o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = ts3;
-        o[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);        // HW_ID: cu / sh / se
-        o[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);       // XCC_ID
-        o[6] = tile;
-        o[7] = tw_sum;
-    }
-#endif
 }
 
 // The GT_PREC_F16X2 twin of gemm_x3p_kernel (two fp16 planes, three products, see above).  It is a SEPARATE body on purpose:
@@ -1371,7 +1268,6 @@ __device__ __forceinline__ void x3p_body(const GemmP& p) {
     constexpr int SMEM = R * X3R_OP > STG ? R * X3R_OP : STG;
     __shared__ __attribute__((aligned(16))) char smem[SMEM];
 
-    X3P_STAMP(0);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = BN == 64 ? wave : wave >> 1, wn = BN == 64 ? 0 : wave & 1;
     const int wrow = BN == 64 ? wm * 32 : wm * 64; // first tile row of this wave
@@ -1402,7 +1298,7 @@ __device__ __forceinline__ void x3p_body(const GemmP& p) {
     int ea[MI];                                    // F16: running exponent of this lane's row in tile i (see x3h_* above)
 #pragma unroll
     for (int i = 0; i < MI; ++i) ea[i] = X3H_E0;
-    // GT_X3_ALT in this kernel (no register to spare for a per-lane sign): the M-side sign alternates per 32-ROW TILE -- a
+    // Sign alternation in this kernel (no register to spare for a per-lane sign): the M-side sign alternates per 32-ROW TILE -- a
     // compile-time constant of the unrolled tile loop for the 64-row wave tile (a source modifier of the split's first
     // instructions), the wave's parity (a scalar) for the 32-row one -- the N-side per column (x3_pack_b_kernel)
     const float tsgn = x3_alt_sign(BN == 64 ? __builtin_amdgcn_readfirstlane(wm) : 0);
@@ -1449,23 +1345,16 @@ __device__ __forceinline__ void x3p_body(const GemmP& p) {
     // iteration, and is consumed one iteration later.  Vector-memory loads retire in order, so a wait for B also waits for
     // every A stage requested before it: with ONE set the loads of B(kt + 1) can only go out behind the MFMAs of B(kt), and
     // their latency (plus that of the A stage requested one iteration earlier) stands in front of every stage's MFMAs --
-    // load, matrix and store time of a launch add up instead of overlapping (tools/ablate_x3.sh: 37 + 15 + 30 = 82 us).
+    // load, matrix and store time of a launch add up instead of overlapping (timing ablations: 37 + 15 + 30 = 82 us).
     using frag_t = std::conditional_t<F16 != 0, f16x8, bf16x8>;    // the MFMA's own operand type: no conversion (= no copy of a
                                                                    // register the load has not filled yet) between load and use
     frag_t bn0[2][PLANES], bn1[2][PLANES];
     auto loadb = [&](int ks, frag_t (&bn)[2][PLANES]) {
-#ifdef GT_ABL_X3_NOLOADB         // ablation: the B fragments are fetched for the first two stages only (timing; wrong results)
-        if (ks > 1) return;
-#endif
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int pl = 0; pl < PLANES; ++pl) {
-#ifdef GT_ABL_X3_NOSPLIT_B       // ablation: every stage reads the same (cache-resident) fragment
-                const char* sp = bbase + pl * bplane + (int64_t)j * p.bp_KS * 1024;
-#else
                 const char* sp = bbase + pl * bplane + ((int64_t)j * p.bp_KS + ks) * 1024;
-#endif
                 asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(bn[j][pl]) : "v"(voff), "s"(sp));
             }
     };
@@ -1501,7 +1390,7 @@ __device__ __forceinline__ void x3p_body(const GemmP& p) {
                         for (int e = 0; e < 16; ++e) acc[i][j][e] *= f;
                     ea[i] = enew;
                 }
-                const float sv = x3h_pow2(ea[i]) * (MI == 1 ? tsgn : ((GT_X3_ALT && (i & 1)) ? -1.f : 1.f));
+                const float sv = x3h_pow2(ea[i]) * (MI == 1 ? tsgn : ((i & 1) ? -1.f : 1.f));
                 uint32_t q[4][2];
 #pragma unroll
                 for (int t = 0; t < 4; ++t) x3h_split_pair(v[2 * t], v[2 * t + 1], sv, q[t]);
@@ -1521,15 +1410,11 @@ __device__ __forceinline__ void x3p_body(const GemmP& p) {
                 continue;
             }
             bf16x8 am[3];
-            if (GT_X3_ALT && (MI == 1 || (i & 1))) {   // M-side: the sign alternates per 32-row tile (see below)
+            if (MI == 1 || (i & 1)) {             // M-side: the sign alternates per 32-row tile (see below)
 #pragma unroll
                 for (int q = 0; q < 8; ++q) v[q] = MI == 1 ? v[q] * tsgn : -v[q];
             }
-#ifdef GT_ABL_X3_NOSPLIT_A       // ablation builds (tools/ablate_x3.sh): timing only, results are wrong
-            for (int pl = 0; pl < PLANES; ++pl) am[pl] = __builtin_bit_cast(bf16x8, u32x4{__float_as_uint(v[0]), __float_as_uint(v[2]), __float_as_uint(v[4]), __float_as_uint(v[6])});
-#else
             x3r_split<3>(v, am);
-#endif
             if constexpr (!F16) {
 #pragma unroll
                 for (int s = 2; s >= 0; --s) {             // plane pairs (pa, pb) with pa + pb = s, smallest terms first
@@ -1552,7 +1437,7 @@ __device__ __forceinline__ void x3p_body(const GemmP& p) {
     // the end of K the A loader reads the zero line into a free slot and B re-reads its last stage -- so the counts hold
     // to the last stage and no load sits under a branch: a conditional asm load makes hipcc allocate fresh registers for
     // it and COPY them into the set at the join, before the data has arrived (seen in the ISA of a first version).
-#define X3P_WAIT_AB_(N, bn)                                                                                            \
+#define X3P_WAIT_AB(N, bn)                                                                                             \
     do {                                                                                                               \
         if constexpr (PLANES == 3)                                                                                     \
             asm volatile("s_waitcnt vmcnt(" #N ")\n\ts_barrier"                                                        \
@@ -1566,26 +1451,11 @@ __device__ __forceinline__ void x3p_body(const GemmP& p) {
                          :                                                                                             \
                          : "memory");                                                                                  \
     } while (0)
-#ifdef GT_X3P_PROF                                 // time spent in the waits of the K loop (wave 0)
-    unsigned long long tw_sum = 0;
-#define X3P_WAIT_AB(N, bn)                                                                                             \
-    do {                                                                                                               \
-        const unsigned long long w0_ = __builtin_amdgcn_s_memrealtime();                                              \
-        X3P_WAIT_AB_(N, bn);                                                                                           \
-        tw_sum += __builtin_amdgcn_s_memrealtime() - w0_;                                                              \
-    } while (0)
-#else
-#define X3P_WAIT_AB(N, bn) X3P_WAIT_AB_(N, bn)
-#endif
     const int klast = nk - 1;
     loadb(0, bn0);
 #pragma unroll
     for (int s = 0; s < R - 1; ++s) issue(s);
-    if (R == 3) X3P_WAIT_AB(2, bn0);               // iteration 0: behind A(0) are the R - 2 other stages of the prologue
-    else if (R == 4) X3P_WAIT_AB(4, bn0);
-    else if (R == 5) X3P_WAIT_AB(6, bn0);
-    else X3P_WAIT_AB(8, bn0);
-    X3P_STAMP(1);
+    X3P_WAIT_AB(4, bn0);                           // iteration 0: behind A(0) are the R - 2 other stages of the prologue
     loadb(klast < 1 ? klast : 1, bn1);
     issue(R - 1);
     stage(0, bn0);
@@ -1604,31 +1474,25 @@ __device__ __forceinline__ void x3p_body(const GemmP& p) {
         X3P_WAIT_AB(2, bn1);
         stage(kt, bn1);
     }
-    X3P_STAMP(2);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the zero stages requested past the end of K: the ring becomes staging
 #undef X3P_WAIT_AB
-#undef X3P_WAIT_AB_
-#ifdef GT_ABL_X3_NOSTORE
-    if (acc[0][0][0] != 12345.678f) return;
-#endif
 
-    if constexpr (F16) {           // un-scale (row exponent of the lane, tile exponent of the packed columns) with the ALT sign
+    if constexpr (F16) {           // un-scale (row exponent of the lane, tile exponent of the packed columns) with the alternating sign
         const int* ebp = reinterpret_cast<const int*>(reinterpret_cast<const char*>(p.Bp) + 2 * bplane) + ((n0 + wn_u * 64) >> 5);
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int et = -(ea[i] + ebp[j]), etc = et < -126 ? -126 : (et > 126 ? 126 : et);
-                const float sg = x3h_pow2(etc) * (MI == 1 ? tsgn : ((GT_X3_ALT && (i & 1)) ? -1.f : 1.f));
+                const float sg = x3h_pow2(etc) * (MI == 1 ? tsgn : ((i & 1) ? -1.f : 1.f));
 #pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] *= (GT_X3_ALT && (e & 1)) ? -sg : sg;
+                for (int e = 0; e < 16; ++e) acc[i][j][e] *= (e & 1) ? -sg : sg;
                 if (et != etc) {       // row amax x tile amax below ~2^-100: the rest of the power of two (no cliff)
 #pragma unroll
                     for (int e = 0; e < 16; ++e) acc[i][j][e] = ldexpf(acc[i][j][e], et - etc);
                 }
             }
     } else {
-#if GT_X3_ALT
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -1638,7 +1502,6 @@ __device__ __forceinline__ void x3p_body(const GemmP& p) {
                     const float sg = MI == 1 ? tsgn : ((i & 1) ? -1.f : 1.f);
                     acc[i][j][e] *= (e & 1) ? -sg : sg;
                 }
-#endif
     }
     __syncthreads();                               // every wave is done with the ring: its first slots become staging
     if constexpr (HN > 0)
@@ -1647,18 +1510,6 @@ __device__ __forceinline__ void x3p_body(const GemmP& p) {
     else
         x3_epilogue<MI>(p, acc, m0 + wrow, n0 + wn * 64, lane, reinterpret_cast<float*>(smem) + wave * X3_EP_STG, 0, 0, 0, 0,
                         bias4);
-#ifdef GT_X3P_PROF
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the block's stores have left
-    X3P_STAMP(3);
-    if (tid == 0 && blockIdx.x < 8192) {
-        unsigned long long* o = x3p_prof + 8 * blockIdx.x;
-        o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = ts3;
-        o[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);        // HW_ID: cu / sh / se
-        o[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);       // XCC_ID
-        o[6] = tile;
-        o[7] = tw_sum;
-    }
-#endif
 }
 
 template <int LA, int HN, int CV, int BN = 128>        // the GT_PREC_F16X2 instances
@@ -1677,7 +1528,7 @@ __global__ __launch_bounds__(256, 3) void gemm_x3h_kernel(const GemmP p) {
 // amax of the two tiles it is about to split (wave reduce + four floats through LDS, the barrier is there anyway), lowers the
 // exponent -- rescaling its accumulators -- when the scaled amax would reach 2^15, and otherwise keeps it, so nothing can
 // overflow and values are resolved to 2^-22 of the largest magnitude the block has seen (the weight gradient is a sum over
-// all tokens: the tensor's scale is the relevant one).  GT_X3_ALT as everywhere: odd rows of both operands enter negated.
+// all tokens: the tensor's scale is the relevant one).  Sign alternation as everywhere: odd rows of both operands enter negated.
 constexpr int X3W_KG = 4;                            // k-groups (8 tokens) per stage
 constexpr int X3W_PLANE = X3W_KG * 128 * 16;         // bytes of one plane of one operand tile: 8 KB
 
@@ -1687,18 +1538,9 @@ constexpr int X3W_PLANE = X3W_KG * 128 * 16;         // bytes of one plane of on
 // (profiles/r05_x3w_prefetch.json).  PF = 2: the request for stage s + 2 is issued when stage s has been split, a full
 // stage of split + MFMA work earlier; 32 more registers (180: two blocks per CU instead of three, four stages per CU in
 // flight instead of three).
-#ifdef GT_X3W_PROF                                 // tools/x3w_prof.py: shader-clock cycles wave 0 of a block spends per phase
-__device__ unsigned long long x3w_prof[8 * 4096];
-extern "C" int gt_debug_x3w_prof(void* dst, long long bytes) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(x3w_prof), (size_t)bytes);
-}
-#define X3W_T(i) { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[i] += now_ - tlast; tlast = now_; }
-#else
-#define X3W_T(i)
-#endif
-
+// PF = 2 is the only instance; the parameter stays part of the kernel's name.
 template <int PF>
-__global__ __launch_bounds__(256, PF == 1 ? 3 : 2) void gemm_x3w_kernel(const GemmP p) {
+__global__ __launch_bounds__(256, 2) void gemm_x3w_kernel(const GemmP p) {
     __shared__ __attribute__((aligned(16))) char smem[4 * X3W_PLANE];      // A planes 0 / 1, B planes 0 / 1
     __shared__ float red[1][4];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1738,7 +1580,7 @@ __global__ __launch_bounds__(256, PF == 1 ? 3 : 2) void gemm_x3w_kernel(const Ge
     // A whole stage (the usual case, block-uniform test): the address of a load is a wave-uniform row pointer (token k0 + e of
     // the operand: scalar registers, advanced by scalar adds) + a per-thread byte offset that never changes -- no vector
     // address arithmetic and no branch per load (the general form below cost ~10 VALU / SALU instructions per load, a
-    // fifth of the split phase this kernel is bound by: tools/x3w_prof.py)
+    // fifth of the split phase this kernel is bound by, in shader-clock stamps per phase)
     const uint32_t voff = (uint32_t)((8 * kg * ldo + (isB ? n0 : m0) + 4 * r4) * (int64_t)sizeof(float));
     const char* rowbase = reinterpret_cast<const char*>(isB ? p.B : p.A);
     // round 5: partial edge tiles (M, N multiples of 32, e.g. ex3's 192 / 384 / 576): a thread whose four rows lie beyond the
@@ -1772,10 +1614,6 @@ __global__ __launch_bounds__(256, PF == 1 ? 3 : 2) void gemm_x3w_kernel(const Ge
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
     int ea = X3H_E0, eb = X3H_E0;                      // block-uniform running exponents of the two operands
     float asum[4] = {0.f, 0.f, 0.f, 0.f};
-#ifdef GT_X3W_PROF
-    unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-    const unsigned long long tbeg = tlast;
-#endif
 
     // one stage: the 32 tokens [k0, k0 + 32) whose values are in v; afterwards v holds the stage PF x 32 tokens further on
     auto stage = [&](f32x4 (&v)[8], int k0) __attribute__((always_inline)) {
@@ -1796,10 +1634,8 @@ __global__ __launch_bounds__(256, PF == 1 ? 3 : 2) void gemm_x3w_kernel(const Ge
                 mx = 0.f;
             }
         }
-        X3W_T(0);                                      // the stage's values have arrived (vmcnt) + amax
         if (lane == 0) red[0][wave] = mx;
         __syncthreads();                               // also: every wave is done reading the previous stage's planes
-        X3W_T(1);
         const float ma = fmaxf(red[0][0], red[0][1]), mb = fmaxf(red[0][2], red[0][3]);
         const int xa = (int)(__float_as_uint(ma) >> 23), xb = (int)(__float_as_uint(mb) >> 23);
         int d = 0;
@@ -1823,7 +1659,7 @@ __global__ __launch_bounds__(256, PF == 1 ? 3 : 2) void gemm_x3w_kernel(const Ge
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {                  // row 4 r4 + c: its eight tokens -> one unit per plane
-            const float sv = (GT_X3_ALT && (c & 1)) ? -sc : sc;          // odd rows enter negated
+            const float sv = (c & 1) ? -sc : sc;          // odd rows enter negated
             uint32_t q[4][2];
 #pragma unroll
             for (int t = 0; t < 4; ++t) x3h_split_pair(v[2 * t][c], v[2 * t + 1][c], sv, q[t]);
@@ -1836,10 +1672,8 @@ __global__ __launch_bounds__(256, PF == 1 ? 3 : 2) void gemm_x3w_kernel(const Ge
             for (int pl = 0; pl < 2; ++pl)
                 *reinterpret_cast<u32x4*>(planes + pl * X3W_PLANE + off) = u32x4{q[0][pl], q[1][pl], q[2][pl], q[3][pl]};
         }
-        X3W_T(2);                                      // exponents, split, plane stores
         if (k0 + 32 * PF < kend) fetch(v, k0 + 32 * PF);   // the values of stage s + PF travel under PF stages of work
         __syncthreads();
-        X3W_T(3);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {               // two MFMA k-steps of 16 tokens
             f16x8 am[2][2], bn[2][2];
@@ -1863,21 +1697,14 @@ __global__ __launch_bounds__(256, PF == 1 ? 3 : 2) void gemm_x3w_kernel(const Ge
                         for (int j = 0; j < 2; ++j) acc[i][j] = mfma32h(bn[j][pb], am[i][pa], acc[i][j]);
                 }
         }
-        X3W_T(4);                                      // fragment reads + MFMA issue
     };
 
-    if (PF == 1) {
-        f32x4 v[8];
-        if (kbeg < kend) fetch(v, kbeg);
-        for (int k0 = kbeg; k0 < kend; k0 += 32) stage(v, k0);
-    } else {
-        f32x4 v0[8], v1[8];
-        if (kbeg < kend) fetch(v0, kbeg);
-        if (kbeg + 32 < kend) fetch(v1, kbeg + 32);
-        for (int k0 = kbeg; k0 < kend; k0 += 64) {
-            stage(v0, k0);
-            if (k0 + 32 < kend) stage(v1, k0 + 32);    // block-uniform
-        }
+    f32x4 v0[8], v1[8];
+    if (kbeg < kend) fetch(v0, kbeg);
+    if (kbeg + 32 < kend) fetch(v1, kbeg + 32);
+    for (int k0 = kbeg; k0 < kend; k0 += 64) {
+        stage(v0, k0);
+        if (k0 + 32 < kend) stage(v1, k0 + 32);        // block-uniform
     }
 
     if (do_acs) {                                      // row sums of A: the four k-group threads of a row
@@ -1891,15 +1718,6 @@ __global__ __launch_bounds__(256, PF == 1 ? 3 : 2) void gemm_x3w_kernel(const Ge
         if (tid < 128 && m0 + tid < p.M)
             p.acs[(int64_t)by * p.M + m0 + tid] = (part[tid] + part[128 + tid]) + (part[256 + tid] + part[384 + tid]);
     }
-#ifdef GT_X3W_PROF
-    if (tid == 0 && blockIdx.x < 4096) {
-        unsigned long long* o = x3w_prof + 8 * blockIdx.x;
-        for (int i = 0; i < 5; ++i) o[i] = tacc[i];
-        o[5] = __builtin_readcyclecounter() - tbeg;
-        o[6] = (unsigned long long)((kend - kbeg + 31) / 32);
-        o[7] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
     // un-scale, undo the sign, store the slab tile: lane (lr, lh) holds row m = .. + 32 i + lr and columns .. + 32 j + 8 g + 4 lh + t
     const int et = -(ea + eb), etc = et < -126 ? -126 : (et > 126 ? 126 : et);
     const float us = x3h_pow2(etc) * x3_alt_sign(lr);
@@ -1927,17 +1745,11 @@ __global__ __launch_bounds__(256, PF == 1 ? 3 : 2) void gemm_x3w_kernel(const Ge
     }
 }
 
-static int x3w_prefetch() {                          // GT_X3W_PF = 1: the single-stage prefetch, for A/B runs
-    static const int pf = [] { const char* e = getenv("GT_X3W_PF"); return e && atoi(e) == 1 ? 1 : 2; }();
-    return pf;
-}
-
 // the launches gemm_x3w_kernel takes: GT_PREC_F16X2, both operands x-contiguous and 16-byte aligned, M / N multiples of 32 (partial
 // edge tiles stage zeros: round 5, ex3's 192 / 384 / 576-wide weights),
 // a long token contraction cut into split-K slabs (raw epilogue), no batching / dropout / second product
 bool x3w_ok(const gt_gemm_desc* d, int split) {
-    static const int on = [] { const char* e = getenv("GT_X3W"); return e ? atoi(e) : 1; }();
-    return on && d->precision == GT_PREC_F16X2 && d->layout_a == 1 && d->layout_b == 1 && split > 1 && d->K >= 16384 &&
+    return d->precision == GT_PREC_F16X2 && d->layout_a == 1 && d->layout_b == 1 && split > 1 && d->K >= 16384 &&
            (d->M & 31) == 0 && (d->N & 31) == 0 && d->M >= 32 && d->N >= 32 && d->batch0 * d->batch1 == 1 && d->K2 == 0 && d->cv_c == 0 &&
            !(d->a_drop.p > 0.f) && ((reinterpret_cast<uintptr_t>(d->A) | reinterpret_cast<uintptr_t>(d->B)) & 15) == 0 &&
            (d->lda & 3) == 0 && (d->ldb & 3) == 0;
@@ -1960,15 +1772,14 @@ bool x3_shape_ok(const gt_gemm_desc* d) {
     // round 6: narrow token products too (N < 96: the 64-column remainder of a width-split 192-wide product -- ex3's d_model --
     // and the d_model = 48 / 64 products of ex4 / ex1), under exactly the conditions that put them on the packed-B kernels
     // (x3_packed_ok), whose 128 x 64 tile instance takes N <= 64; they ran on the fp32 MFMA engine until now
-    static const int narrow = [] { const char* e = getenv("GT_X3_NARROW"); return e ? atoi(e) : 1; }();
-    if (narrow && d->cv_c == 0 && d->N >= 16 && d->N < 96 && d->M >= 16384 && d->M >= 8 * (int64_t)d->N && d->K >= 16 &&
+    if (d->cv_c == 0 && d->N >= 16 && d->N < 96 && d->M >= 16384 && d->M >= 8 * (int64_t)d->N && d->K >= 16 &&
         (d->precision == GT_PREC_BF16X3 || d->precision == GT_PREC_F16X2) &&
         (d->K & 3) == 0 && d->layout_a == 0 && d->batch0 * d->batch1 == 1 && d->K2 == 0 && !d->a_colsum && d->split_k == 1 &&
         d->ep_mode == GT_EP_NORMAL && (d->lda & 3) == 0 && (reinterpret_cast<uintptr_t>(d->A) & 15) == 0)
         return true;
     // ... and the token-contracted weight gradients of the narrow models (ex1: d_model 64, ffn 128): gemm_x3w_kernel takes
     // partial 128-blocks since round 5, a lone 32 / 64-wide block is the same code path (they ran on the fp32 engine)
-    if (narrow && d->precision == GT_PREC_F16X2 && d->layout_a == 1 && d->layout_b == 1 && d->split_k == 0 && d->K >= 16384 &&
+    if (d->precision == GT_PREC_F16X2 && d->layout_a == 1 && d->layout_b == 1 && d->split_k == 0 && d->K >= 16384 &&
         d->M >= 32 && d->N >= 32 && (d->M & 31) == 0 && (d->N & 31) == 0 && x3w_ok(d, 2))
         return true;
     return d->M >= 96 && d->N >= 96 && d->K >= 16;
@@ -1985,25 +1796,14 @@ bool x3_headnorm_ok(const GemmP& p, int layout_a, int layout_b, int planes) {
     return al(p.bias) && al(p.hn_gamma) && al(p.hn_beta) && al(p.hn_out) && al(p.hn_stats);
 }
 
-// ring depth: 3 stages x 16 KB = 48 KB, three blocks per CU (default; measured 38.0 vs 38.35 ms/step at B128) or
-// GT_X3_RING_DEPTH=4: 4 x 16 KB = 64 KB, two blocks per CU
-static int x3_ring_depth() {
-    static const int d = [] { const char* e = getenv("GT_X3_RING_DEPTH"); return (e && atoi(e) == 4) ? 4 : 3; }();
-    return d;
-}
-
-template <int LA, int LB, int R>
-static void x3_launch_ring(const GemmP& p, int planes, dim3 grid, hipStream_t st) {
-    if (planes == 1) hipLaunchKernelGGL((gemm_x3r_kernel<LA, LB, 1, R>), grid, dim3(256), 0, st, p);
-    else if (planes == 2) hipLaunchKernelGGL((gemm_x3r_kernel<LA, LB, 2, R>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((gemm_x3r_kernel<LA, LB, 3, R>), grid, dim3(256), 0, st, p);
-}
-
+// ring depth 3: 3 stages x 16 KB = 48 KB, three blocks per CU (measured 38.0 ms/step at B128 against 38.35 for depth 4,
+// 64 KB and two blocks per CU)
 template <int LA, int LB>
 static void x3_launch_planes(const GemmP& p, int planes, bool ring, dim3 grid, hipStream_t st) {
     if (ring) {
-        if (x3_ring_depth() == 3) x3_launch_ring<LA, LB, 3>(p, planes, grid, st);
-        else x3_launch_ring<LA, LB, 4>(p, planes, grid, st);
+        if (planes == 1) hipLaunchKernelGGL((gemm_x3r_kernel<LA, LB, 1, 3>), grid, dim3(256), 0, st, p);
+        else if (planes == 2) hipLaunchKernelGGL((gemm_x3r_kernel<LA, LB, 2, 3>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((gemm_x3r_kernel<LA, LB, 3, 3>), grid, dim3(256), 0, st, p);
         return;
     }
     if (planes == 1) hipLaunchKernelGGL((gemm_x3_kernel<LA, LB, 1>), grid, dim3(256), 0, st, p);
@@ -2011,17 +1811,12 @@ static void x3_launch_planes(const GemmP& p, int planes, bool ring, dim3 grid, h
     else hipLaunchKernelGGL((gemm_x3_kernel<LA, LB, 3>), grid, dim3(256), 0, st, p);
 }
 
-static bool x3_use_ring(const GemmP& p, int layout_a, int layout_b) {
-    static const int force = [] { const char* e = getenv("GT_X3_RING"); return e ? atoi(e) : -1; }();   // tuning knob
-    return force == 0 ? false : x3r_ok(p, layout_a, layout_b);
-}
-
 int x3_launch(const GemmP& p, int layout_a, int layout_b, int planes, unsigned tiles, unsigned split, unsigned batch,
               hipStream_t st) {
     if (planes < 1 || planes > 3) return GT_EINVAL;
     const dim3 grid(tiles, split, batch);
     const int lay = layout_a * 2 + layout_b;
-    const bool ring = x3_use_ring(p, layout_a, layout_b);
+    const bool ring = x3r_ok(p, layout_a, layout_b);
     if (p.Bp) {                                    // packed-B kernel (x3_packed_ok said yes)
         const int hn = p.ep_mode == GT_EP_HEADNORM ? p.hn_dk : 0;
         if (hn && !x3_headnorm_ok(p, layout_a, 0, planes)) return GT_ENOTSUP;
@@ -2058,15 +1853,9 @@ int x3_launch(const GemmP& p, int layout_a, int layout_b, int planes, unsigned t
     }
     if (p.ep_mode == GT_EP_HEADNORM) {
         if (!x3_headnorm_ok(p, layout_a, layout_b, planes)) return GT_ENOTSUP;
-        if (x3_ring_depth() == 3) {
-            if (p.hn_dk == 16) hipLaunchKernelGGL((gemm_x3r_kernel<0, 0, 3, 3, 16>), grid, dim3(256), 0, st, p);
-            else if (p.hn_dk == 32) hipLaunchKernelGGL((gemm_x3r_kernel<0, 0, 3, 3, 32>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((gemm_x3r_kernel<0, 0, 3, 3, 64>), grid, dim3(256), 0, st, p);
-        } else {
-            if (p.hn_dk == 16) hipLaunchKernelGGL((gemm_x3r_kernel<0, 0, 3, 4, 16>), grid, dim3(256), 0, st, p);
-            else if (p.hn_dk == 32) hipLaunchKernelGGL((gemm_x3r_kernel<0, 0, 3, 4, 32>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((gemm_x3r_kernel<0, 0, 3, 4, 64>), grid, dim3(256), 0, st, p);
-        }
+        if (p.hn_dk == 16) hipLaunchKernelGGL((gemm_x3r_kernel<0, 0, 3, 3, 16>), grid, dim3(256), 0, st, p);
+        else if (p.hn_dk == 32) hipLaunchKernelGGL((gemm_x3r_kernel<0, 0, 3, 3, 32>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((gemm_x3r_kernel<0, 0, 3, 3, 64>), grid, dim3(256), 0, st, p);
         GT_LAUNCH_CHECK();
         return 0;
     }
@@ -2088,15 +1877,11 @@ int x3_launch(const GemmP& p, int layout_a, int layout_b, int planes, unsigned t
         return 0;
     }
     if (p.wg_f16) {                                // GT_PREC_F16X2 weight gradient (x3w_ok said yes)
-        const int pf = x3w_prefetch();
-        // map 0: tile-major grid; 1: chunk-major within an XCD (default since round 6: the same time as 2 at three tiles, and
-        // the narrower operand is fetched once instead of once per tile -- 727 -> ~500 MB at [384 x 128]); 2: that for two tiles only
-        static const int map = [] { const char* e = getenv("GT_X3W_MAP"); return e ? atoi(e) : 1; }();
+        // a 1-D grid, chunk-major within an XCD (round 6: the same time as the tile-major grid at three tiles, and the
+        // narrower operand is fetched once instead of once per tile -- 727 -> ~500 MB at [384 x 128])
         GemmP q = p;
-        q.x3w_map = map == 1 || (map == 2 && tiles == 2);
-        const dim3 g1 = q.x3w_map ? dim3(8u * ((split + 7) / 8) * tiles) : grid;
-        if (pf == 1) hipLaunchKernelGGL(gemm_x3w_kernel<1>, g1, dim3(256), 0, st, q);
-        else hipLaunchKernelGGL(gemm_x3w_kernel<2>, g1, dim3(256), 0, st, q);
+        q.x3w_map = 1;
+        hipLaunchKernelGGL(gemm_x3w_kernel<2>, dim3(8u * ((split + 7) / 8) * tiles), dim3(256), 0, st, q);
         GT_LAUNCH_CHECK();
         return 0;
     }
@@ -2110,10 +1895,9 @@ int x3_launch(const GemmP& p, int layout_a, int layout_b, int planes, unsigned t
 
 // ---- packed-B path: host side ---------------------------------------------------------------------------------------
 // B small next to A (a weight against >= 16384 token rows), three planes, one launch (no batching, split-K, second
-// product or row-sum by-product), operands the direct loads can take.  GT_X3_PACKED=0 switches it off (A/B runs).
+// product or row-sum by-product), operands the direct loads can take.
 bool x3_packed_ok(const gt_gemm_desc* d, int planes, int split) {
-    static const int on = [] { const char* e = getenv("GT_X3_PACKED"); return e ? atoi(e) : 1; }();
-    if (!on || planes != 3 || split != 1 || d->batch0 * d->batch1 != 1 || d->K2 > 0 || d->a_colsum) return false;
+    if (planes != 3 || split != 1 || d->batch0 * d->batch1 != 1 || d->K2 > 0 || d->a_colsum) return false;
     if (d->cv_c > 0 && d->cv_wgrad) return false;
     // below 16384 rows the extra (pack) launch is not paid back -- except for the implicit convolutions, whose K = 9 C makes
     // the product long enough (round 5: the down-scaler chain runs at every batch, no library convolution below B = 3)
@@ -2184,20 +1968,18 @@ const char* x3_kernel_name(const GemmP& p, int layout_a, int layout_b, int plane
         return buf;
     }
     if (hn_dk > 0) {
-        snprintf(buf, sizeof(buf), "void gt::gemm_x3r_kernel<0, 0, 3, %d, %d, 0>(gt::GemmP)", x3_ring_depth(), hn_dk);
+        snprintf(buf, sizeof(buf), "void gt::gemm_x3r_kernel<0, 0, 3, 3, %d, 0>(gt::GemmP)", hn_dk);
         return buf;
     }
     if (p.wg_f16) {
-        snprintf(buf, sizeof(buf), "void gt::gemm_x3w_kernel<%d>(gt::GemmP)", x3w_prefetch());
-        return buf;
+        return "void gt::gemm_x3w_kernel<2>(gt::GemmP)";
     }
     if (p.cv_C > 0 && p.cv_wgrad)
         snprintf(buf, sizeof(buf), "void gt::gemm_x3r_kernel<1, 1, %d, 3, 0, 2>(gt::GemmP)", planes);
     else if (p.cv_C > 0)
         snprintf(buf, sizeof(buf), "void gt::gemm_x3r_kernel<0, 0, %d, 3, 0, 1>(gt::GemmP)", planes);
-    else if (x3_use_ring(p, layout_a, layout_b))
-        snprintf(buf, sizeof(buf), "void gt::gemm_x3r_kernel<%d, %d, %d, %d, 0, 0>(gt::GemmP)", layout_a, layout_b, planes,
-                 x3_ring_depth());
+    else if (x3r_ok(p, layout_a, layout_b))
+        snprintf(buf, sizeof(buf), "void gt::gemm_x3r_kernel<%d, %d, %d, 3, 0, 0>(gt::GemmP)", layout_a, layout_b, planes);
     else
         snprintf(buf, sizeof(buf), "void gt::gemm_x3_kernel<%d, %d, %d>(gt::GemmP)", layout_a, layout_b, planes);
     return buf;

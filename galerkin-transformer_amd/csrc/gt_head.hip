@@ -19,7 +19,6 @@
 // The backward splits the hidden axis over a PAIR of waves (64 each; the full 128 would need > 256 registers
 // per lane for the dW1 accumulators): the pair exchanges its two partial dX^T tiles through LDS once per tile.
 #include "gt_common.h"
-#include <atomic>
 #include <algorithm>
 
 namespace gt {
@@ -474,10 +473,6 @@ __global__ __launch_bounds__(256, 2) void head_fwd16_kernel(const HeadP p) {
     }
 }
 
-#ifndef H16_ABL
-#define H16_ABL 0         // timing ablations of head_bwd16_kernel (wrong results): 1 no (3) * 2 no (2) * 4 no loop barriers * 8 no shuffles * 16 no (1)
-#endif
-#define H16_SHFL(v, o) ((H16_ABL & 8) ? (v) : __shfl_xor((v), (o), 64))
 constexpr int DH16P = 68;                            // floats per row of a wave's dh tile [32 rows][64 hidden]
 constexpr int H16_LIMIT = 15, H16_TARGET = 13;       // running exponent of (3): scaled |x| kept below 2^15, reset to 2^13
 // dynamic LDS of head_bwd16_kernel: W1 fragments (1) 16 KB | W1^T fragments (2) 16 KB | b1, w2 | dh tiles 4 x 8.5 KB |
@@ -545,8 +540,8 @@ __global__ __launch_bounds__(256, 2) void head_bwd16_kernel(const HeadP p) {
             float m = 0.f;
 #pragma unroll
             for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(xs[e]));
-            m = fmaxf(m, H16_SHFL(m, 16));
-            m = fmaxf(m, H16_SHFL(m, 32));
+            m = fmaxf(m, __shfl_xor(m, 16, 64));
+            m = fmaxf(m, __shfl_xor(m, 32, 64));
             const int ex = h16_exp_for(m);
             h16_split8(xs, h16_pow2(ex), xh[u], xl[u]);
             us[u] = h16_pow2(-ex) * usW;
@@ -568,8 +563,7 @@ __global__ __launch_bounds__(256, 2) void head_bwd16_kernel(const HeadP p) {
                     const int ft = (hb >> 4) + mt;   // hidden tile of the tensor
                     const hf16x8 wh = __builtin_bit_cast(hf16x8, sW1[ft * 64 + lane]);
                     const hf16x8 wl = __builtin_bit_cast(hf16x8, sW1[512 + ft * 64 + lane]);
-                    const f32x4 acc = (H16_ABL & 16) ? f32x4{xm[u], g[u], xm[u], g[u]}
-                                                     : h16_mma3(wh, wl, xh[u], xl[u], f32x4{0.f, 0.f, 0.f, 0.f});
+                    const f32x4 acc = h16_mma3(wh, wl, xh[u], xl[u], f32x4{0.f, 0.f, 0.f, 0.f});
                     const f32x4 bv = *reinterpret_cast<const f32x4*>(&sB1[hb + 16 * mt + 4 * kq]);
                     const f32x4 wv = *reinterpret_cast<const f32x4*>(&sW2[hb + 16 * mt + 4 * kq]);
 #pragma unroll
@@ -585,8 +579,8 @@ __global__ __launch_bounds__(256, 2) void head_bwd16_kernel(const HeadP p) {
                 }
                 // the row's exponent over this wave's 64 hidden units; the scaled values serve (2) from registers and
                 // (3) from the LDS tile
-                dm = fmaxf(dm, H16_SHFL(dm, 16));
-                dm = fmaxf(dm, H16_SHFL(dm, 32));
+                dm = fmaxf(dm, __shfl_xor(dm, 16, 64));
+                dm = fmaxf(dm, __shfl_xor(dm, 32, 64));
                 const int ed = h16_exp_for(dm);
                 const float sd = h16_pow2(ed);
                 // a row without gradient (padding, or every unit switched off) takes no part in (3): factor 0, and it
@@ -603,7 +597,7 @@ __global__ __launch_bounds__(256, 2) void head_bwd16_kernel(const HeadP p) {
                 }
                 // (2) partial dX^T over this wave's hidden half: k-step t = hidden tiles 2t, 2t + 1 of the half
 #pragma unroll
-                for (int t = 0; t < ((H16_ABL & 2) ? 0 : 2); ++t) {
+                for (int t = 0; t < 2; ++t) {
                     const float dv8[8] = {d[2 * t][0], d[2 * t][1], d[2 * t][2], d[2 * t][3],
                                           d[2 * t + 1][0], d[2 * t + 1][1], d[2 * t + 1][2], d[2 * t + 1][3]};
                     hf16x8 dhi, dlo;
@@ -631,9 +625,9 @@ __global__ __launch_bounds__(256, 2) void head_bwd16_kernel(const HeadP p) {
         for (int e = 0; e < 8; ++e) {
             const int64_t row = std::min<int64_t>(m0 + 8 * kq + e, p.T - 1);
 #pragma unroll
-            for (int ti = 0; ti < 2; ++ti) xr[ti][e] = (active && !(H16_ABL & 1)) ? p.X[row * HK + 16 * ti + j] : 0.f;
+            for (int ti = 0; ti < 2; ++ti) xr[ti][e] = active ? p.X[row * HK + 16 * ti + j] : 0.f;
         }
-        if (!(H16_ABL & 4)) __syncthreads();
+        __syncthreads();
         if (active && p.dX) {
 #pragma unroll
             for (int u = 0; u < 2; ++u)
@@ -644,11 +638,11 @@ __global__ __launch_bounds__(256, 2) void head_bwd16_kernel(const HeadP p) {
                     *reinterpret_cast<f32x4*>(p.dX + (m0 + 16 * u + j) * HK + 16 * half + 4 * kq) = dxv;
                 }
         }
-        if (active && !(H16_ABL & 1)) {
+        if (active) {
             // (3): one exponent for the wave.  mag = largest |x| 2^-e_j of the 32 rows
             float mag = fmaxf(rowmag[0], rowmag[1]);
 #pragma unroll
-            for (int o = 1; o < 16; o <<= 1) mag = fmaxf(mag, H16_SHFL(mag, o));
+            for (int o = 1; o < 16; o <<= 1) mag = fmaxf(mag, __shfl_xor(mag, o, 64));
             const int xe = (int)(__float_as_uint(mag) >> 23);
             if (xe != 0 && xe + cexp - 127 >= H16_LIMIT) {             // wave-uniform
                 const int cn = H16_TARGET + 127 - xe, dlt = cn - cexp;
@@ -690,7 +684,7 @@ __global__ __launch_bounds__(256, 2) void head_bwd16_kernel(const HeadP p) {
                 for (int ti = 0; ti < 2; ++ti) accW[mt][ti] = h16_mma3(ah, al, bh[ti], bl[ti], accW[mt][ti]);
             }
         }
-        if (!(H16_ABL & 4)) __syncthreads();         // the partner has read the exchange tile
+        __syncthreads();                             // the partner has read the exchange tile
     }
     // un-scale the weight-gradient accumulators
     {
@@ -771,11 +765,8 @@ static int head_check(const float* X, int64_t T, int32_t K, int32_t N, int32_t n
 }
 
 // GT_PREC_F16X2 runs the two-term fp16 kernels; every other value of `precision` the fp32-MFMA ones (bit-exact fp32
-// products: what GT_PREC_F32 promises, and what the bf16 modes have always used here).  GT_HEAD_F16=0: fp32 kernels always.
-static bool head_use_f16(int32_t precision) {
-    static const int on = [] { const char* e = getenv("GT_HEAD_F16"); return e ? atoi(e) : 1; }();
-    return on && precision == GT_PREC_F16X2;
-}
+// products: what GT_PREC_F32 promises, and what the bf16 modes have always used here).
+static bool head_use_f16(int32_t precision) { return precision == GT_PREC_F16X2; }
 
 extern "C" int gt_mlp_head_fwd(const float* X, int64_t T, int32_t K, int32_t N, int32_t n_out, const float* W1,
                                const float* b1, const float* w2, const float* b2, int32_t act, int32_t precision,
@@ -804,12 +795,6 @@ extern "C" int64_t gt_mlp_head_bwd_ws_bytes(int64_t T) {
     return T > 0 ? (int64_t)head_blocks(T, 2) * HSLAB * (int64_t)sizeof(float) : 0;
 }
 
-template <typename Kern>
-static int head16_allow_lds(Kern k) {                 // 76 KB of dynamic LDS: opt in once per instance
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, H16_SMEM);
-    return e == hipSuccess ? 0 : (int)e;
-}
-
 extern "C" int gt_mlp_head_bwd(const float* X, int64_t T, int32_t K, int32_t N, int32_t n_out, const float* W1,
                                const float* b1, const float* w2, int32_t act, int32_t precision, const float* g,
                                float* dX, float* dW1, float* db1, float* dw2, float* db2, void* ws, int64_t ws_bytes,
@@ -834,17 +819,11 @@ extern "C" int gt_mlp_head_bwd_gated(const float* X, int64_t T, int32_t K, int32
         const int64_t n32 = (T + 31) / 32;
         const int blocks16 = (int)std::min<int64_t>(512, (n32 + 1) / 2);
         HeadP q{X, W1, b1, w2, nullptr, g, nullptr, dX, reinterpret_cast<float*>(ws), T, (int)((T + 15) / 16), dx_gate};
-        // the opt-in is per DEVICE: one bit per device ordinal (a process driving several GPUs)
-        static std::atomic<uint64_t> raised{0};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const uint64_t dbit = 1ull << (dev & 63);
-        if (!(raised.load(std::memory_order_acquire) & dbit)) {
-            if (head16_allow_lds(head_bwd16_kernel<GT_ACT_NONE>) | head16_allow_lds(head_bwd16_kernel<GT_ACT_RELU>) |
-                head16_allow_lds(head_bwd16_kernel<GT_ACT_SILU>))
-                return GT_ENOTSUP;
-            raised.fetch_or(dbit, std::memory_order_release);
-        }
+        // 76 KB of dynamic LDS: opt in once per device and instance
+        if (gt_allow_dynamic_lds<head_bwd16_kernel<GT_ACT_NONE>>(H16_SMEM) ||
+            gt_allow_dynamic_lds<head_bwd16_kernel<GT_ACT_RELU>>(H16_SMEM) ||
+            gt_allow_dynamic_lds<head_bwd16_kernel<GT_ACT_SILU>>(H16_SMEM))
+            return GT_ENOTSUP;
         if (act == GT_ACT_SILU)
             hipLaunchKernelGGL((head_bwd16_kernel<GT_ACT_SILU>), dim3(blocks16), dim3(256), H16_SMEM, st, q);
         else if (act == GT_ACT_RELU)

@@ -1429,14 +1429,13 @@ __global__ __launch_bounds__(256) void modemix_bwd_kernel(
 // batch slices per mode block: enough blocks for ~3 per CU, at least 8 samples per slice
 static inline int modemix_slices(int B, int Q) { return std::max(1, std::min(ceil_div(768, Q), ceil_div(B, 8))); }
 
-// kernels whose dynamic LDS may exceed 64 KiB opt in once (host-side attribute, not a stream op)
-template <typename K>
-static int allow_big_lds(K kernel, size_t bytes) {
+// kernels whose dynamic LDS may exceed 64 KiB opt in to the whole 160 KiB once per device (host-side attribute, not a
+// stream op)
+template <auto K>
+static int allow_big_lds(size_t bytes) {
     if (bytes <= 64 * 1024) return 0;
     if (bytes > 160 * 1024) return GT_ENOTSUP;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    return e == hipSuccess ? 0 : (int)e;
+    return gt_allow_dynamic_lds<K>(160 * 1024);
 }
 
 static inline int grid_for(int64_t n, int block = 256, int cap = 4096) {
@@ -1690,7 +1689,7 @@ extern "C" int gt_galerkin_finalize_fwd(const float* slabs, int32_t n_slabs, int
     // (few (batch, head) pairs: four rows per block as before, for the parallelism of the slab sums)
     const int FIN_RB = B * h >= 256 ? fin_rows_per_block(DP) : 4;
     const size_t lds = ((size_t)FIN_RB * DP + (size_t)d * DP) * sizeof(float);
-    if (int rc = allow_big_lds(galerkin_fin_fwd_kernel, lds)) return rc;
+    if (int rc = allow_big_lds<galerkin_fin_fwd_kernel>(lds)) return rc;
     hipLaunchKernelGGL(galerkin_fin_fwd_kernel, dim3(B * h, (DP + FIN_RB - 1) / FIN_RB), dim3(256), lds, (hipStream_t)stream, slabs,
                        n_slabs, slab_stride, h, DP, Dr, d, 1.f / (float)n_tokens, mask,
                        make_drop(mask ? nullptr : drop), Wfc, Mt, P, Pv, pos_dim, FIN_RB);
@@ -1712,7 +1711,7 @@ extern "C" int gt_galerkin_finalize_bwd(const float* dPt, const float* Mt, const
     const size_t lds = ((size_t)((DP + parts - 1) / parts) * (d + 1) + (parts > 1 ? (size_t)DP * ((d + parts - 1) / parts + 1) : 0) +
                         (size_t)d * DP + (size_t)DP * DP) * sizeof(float);
     if ((DP & 3) || (reinterpret_cast<uintptr_t>(dM) & 15)) return GT_EINVAL;
-    if (int rc = allow_big_lds(galerkin_fin_bwd_kernel, lds)) return rc;
+    if (int rc = allow_big_lds<galerkin_fin_bwd_kernel>(lds)) return rc;
     hipLaunchKernelGGL(galerkin_fin_bwd_kernel, dim3(B * h, parts), dim3(256), lds, (hipStream_t)stream, dPt, Mt,
                        mask, make_drop(mask ? nullptr : drop), Wfc, h, DP, Dr, d, 1.f / (float)n_tokens, dM,
                        dWfc_slabs);
@@ -1768,7 +1767,7 @@ extern "C" int gt_modemix_fwd(const float* X, const float* W, int32_t B, int32_t
         return GT_EINVAL;
     if ((reinterpret_cast<uintptr_t>(W) & 7) != 0) return GT_EALIGN;
     const size_t lds = ((size_t)2 * Cin * Cout + (size_t)MM_BCH * 2 * Cin) * sizeof(float);
-    if (int rc = allow_big_lds(modemix_fwd_kernel, lds)) return rc;
+    if (int rc = allow_big_lds<modemix_fwd_kernel>(lds)) return rc;
     hipLaunchKernelGGL(modemix_fwd_kernel, dim3(Q, modemix_slices(B, Q)), dim3(256), lds, (hipStream_t)stream, X, W, B,
                        Q, Cin, Cout, x_bstride, y_bstride, q_total_x, q_total_y, q_off, Y);
     GT_LAUNCH_CHECK();
@@ -1801,11 +1800,11 @@ extern "C" int gt_modemix_bwd(const float* X, const float* W, const float* dY, i
     }
     const dim3 grid((unsigned)Q, (unsigned)S);
     if (Cin * Cout <= 8 * 256) {
-        if (int rc = allow_big_lds(modemix_bwd_kernel<8>, lds)) return rc;
+        if (int rc = allow_big_lds<modemix_bwd_kernel<8>>(lds)) return rc;
         hipLaunchKernelGGL(modemix_bwd_kernel<8>, grid, dim3(256), lds, (hipStream_t)stream, X, W, dY, B, Q, Cin,
                            Cout, x_bstride, y_bstride, q_total_x, q_total_y, q_off, dX, dWk);
     } else {
-        if (int rc = allow_big_lds(modemix_bwd_kernel<24>, lds)) return rc;
+        if (int rc = allow_big_lds<modemix_bwd_kernel<24>>(lds)) return rc;
         hipLaunchKernelGGL(modemix_bwd_kernel<24>, grid, dim3(256), lds, (hipStream_t)stream, X, W, dY, B, Q, Cin,
                            Cout, x_bstride, y_bstride, q_total_x, q_total_y, q_off, dX, dWk);
     }
@@ -1838,8 +1837,7 @@ extern "C" int gt_galerkin_ktv_affine(const float* Kp, const float* Vp, const fl
     dim3 grid((unsigned)n_slabs, (unsigned)B);
     hipStream_t st = (hipStream_t)stream;
     // LDS-staged rows (16-byte loads of whole contiguous token tiles): one head per wave, 16 * h * DP floats per operand tile
-    static const int lds_on = [] { const char* e = getenv("GT_KTV_LDS"); return e ? atoi(e) : 1; }();
-    if (lds_on && h <= 4 && h * DP <= 256 && ((reinterpret_cast<uintptr_t>(Kp) | reinterpret_cast<uintptr_t>(Vp)) & 15) == 0) {
+    if (h <= 4 && h * DP <= 256 && ((reinterpret_cast<uintptr_t>(Kp) | reinterpret_cast<uintptr_t>(Vp)) & 15) == 0) {
         const size_t lds = (size_t)2 * 2 * KTV_TT * h * DP * sizeof(float);
         switch (dk / 16) {
             case 1: hipLaunchKernelGGL(galerkin_ktv_lds_kernel<1>, grid, dim3(256), lds, st, Kp, Vp, n, h, DP, p, chunk, slabs, B, gamma, beta); break;

@@ -595,16 +595,11 @@ static_assert(CR_CH == 16, "conv_resize_fwd_kernel packs the decisions of its 16
 // so a thread walks OUTPUT pixels (coalesced reads of g and y, no gather, the same 3x3 patches as the forward)
 // and accumulates dW for CRB_CG channels in registers over CRB_PXT pixels before one block reduction.
 constexpr int CRB_PXT = 8;
-#ifndef GT_CRB_CG
-#define GT_CRB_CG 8
-#endif
-constexpr int CRB_CG = GT_CRB_CG;
+constexpr int CRB_CG = 8;
 static_assert(CRB_CG % 4 == 0 && CRB_CG >= 4, "the channels-last paths read a pixel's CRB_CG channels as float4 groups");
-#ifndef GT_CRB_WAVES                               // resident waves per SIMD the one-channel instance is compiled for
-#define GT_CRB_WAVES 2
-#endif
+// the one-channel instance is compiled for two resident waves per SIMD
 template <int CIN, bool BITS = false, int ACT = GT_ACT_RELU>
-__global__ __launch_bounds__(256, (CIN == 1 ? GT_CRB_WAVES : 1)) void conv_resize_bwd_kernel(const ConvResizeP p) {
+__global__ __launch_bounds__(256, (CIN == 1 ? 2 : 1)) void conv_resize_bwd_kernel(const ConvResizeP p) {
     static_assert(!BITS || CRB_CG == 8, "the recorded decisions are read as one 32-bit half word: eight channels per thread");
     static_assert(!BITS || ACT == GT_ACT_RELU, "decision bits describe ReLUs");
     __shared__ float sw[BITS ? 1 : CRB_CG * CIN * 9];
@@ -1154,7 +1149,7 @@ static int conv_resize_bwd(const float* g, const float* y, const float* x, const
                            int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t Ho, int32_t Wo,
                            const gt_dropout* drop, int32_t act, float* dw, void* ws, int64_t ws_bytes, int y_nhwc,
                            const void* bits, void* stream) {
-    if (bits && (!y_nhwc || (Cout & 15) || CRB_CG != 8 || (reinterpret_cast<uintptr_t>(bits) & 7) || act != GT_ACT_RELU))
+    if (bits && (!y_nhwc || (Cout & 15) || (reinterpret_cast<uintptr_t>(bits) & 7) || act != GT_ACT_RELU))
         return GT_ENOTSUP;
     const bool no_y = bits || act == GT_ACT_SILU;    // the SiLU backward re-evaluates both activations: y is not read
     if (int rc = check_conv_resize(x, w, no_y ? (const void*)g : (const void*)y, B, Cin, Cout, H, W, Ho, Wo, drop, act)) return rc;

@@ -272,9 +272,9 @@ int     gt_gemm_kernel_name(const gt_gemm_desc* d, char* buf, int32_t n);
  *     hid[t][:] = dropout_h( act( x[t] W1^T + b1 ) )             [T, f]  written to HBM (the backward reads it)
  *     out[t][:] = res[t] + dropout_o( hid[t] W2^T + b2 )         [T, d]  (res may be NULL)
  * in ONE launch: a block owns 64 token rows and keeps their hidden tile in LDS between the two contractions, so the hidden
- * activation is never read back in the forward.  Value for value the arithmetic of the two gt_gemm launches it replaces
- * (same packed planes, same running exponents, same product order, same dropout indices t*f + j / t*d + c): bit-identical
- * results.  x [T, d], W1 [f, d], W2 [d, f] dense fp32, 16-byte aligned; act = GT_ACT_RELU | GT_ACT_NONE.
+ * activation is never read back in the forward.  The arithmetic of the two gt_gemm launches it replaces (same packed
+ * planes, same product order, same dropout indices t*f + j / t*d + c): bit-identical results with GT_FFN_PRESPLIT=0 (same
+ * running exponents too; no decision bits), within about 5e-7 of them in the default pre-split form.  x [T, d], W1 [f, d], W2 [d, f] dense fp32, 16-byte aligned; act = GT_ACT_RELU | GT_ACT_NONE.
  * w1_packed / w2_packed: both NULL (the call packs the weights into ws, gt_ffn_fwd_ws_bytes) or the buffers
  * gt_gemm_pack_b_many filled for the products [T, d] x W1^T and [T, f] x W2^T (gt_gemm_desc.b_packed of those).
  * Implemented for d = 128, f = 256, T >= 16384 (else GT_ENOTSUP: two gt_gemm launches do the same).

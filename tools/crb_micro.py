@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Fused conv0 + resize (gt_conv3x3_resize_fwd/bwd_nhwc) in isolation at the ex2 B = 128 shape: microseconds per launch.
-With and without the recorded decisions (relu_bits).  GT_HIP_LIB selects a library variant (GT_CRB_WAVES builds).
+With and without the recorded decisions (relu_bits).
 
     python tools/crb_micro.py [B]
 """

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One encoder layer (C2 sizes) at batch B through the HIP path vs the CPU oracle: rel-L2 of output, input gradient and
-every parameter gradient as one JSON line.  Run it under different switches (GT_X3_PACKED, GT_DUAL_STREAM, GT_PRECISION,
+every parameter gradient as one JSON line.  Run it under different switches (GT_DUAL_STREAM, GT_PRECISION,
 GT_PLAIN_TILES, GT_DKV_LN, GT_X3Q ...) to find which kernel a parity gap belongs to.  usage: parity_probe.py [B] [f64]"""
 import json
 import os

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Split-operand token GEMMs in isolation at the ex2 B = 128 shapes (T = 128 * 43 * 43 rows): microseconds, useful
 TFLOP/s and algorithmic GB/s per launch, rotating over three buffer sets so the 256 MB infinity cache does not flatter
-the numbers.  GT_HIP_LIB selects a library variant (tools/ablate_x3.sh builds: the ablations give wrong results, only the
-time is read).
+the numbers.
 
     python tools/x3_micro.py [B]
 """

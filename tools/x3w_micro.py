@@ -1,8 +1,6 @@
 #!/usr/bin/env python3
 """Token-contracted weight gradients (gemm_x3w_kernel + its split-K reduce) in isolation at the ex2 B = 128 shapes:
-dW[M][N] = A[T][M]^T B[T][N], T = 128 * 43 * 43, rotating over three operand sets.  Environment switches read by the
-library: GT_X3W_PF (1 | 2: stages of operand values in flight per thread), GT_X3W_MAP (0 tile-major grid, 1 chunk-major
-inside an XCD, 2 = that for two output tiles only).
+dW[M][N] = A[T][M]^T B[T][N], T = 128 * 43 * 43, rotating over three operand sets.
 
     python tools/x3w_micro.py [B]
 """
@@ -21,7 +19,7 @@ def main():
     dev = torch.device("cuda:0")
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
     T = B * 43 * 43
-    out = {"PF": os.environ.get("GT_X3W_PF", "2"), "MAP": os.environ.get("GT_X3W_MAP", "2"), "T": T}
+    out = {"T": T}
     for M, N in ((128, 128), (128, 256), (256, 128), (384, 128)):
         sets = [(torch.randn(T, M, device=dev), torch.randn(T, N, device=dev), torch.empty(M, N, device=dev),
                  torch.empty(M, device=dev)) for _ in range(3)]

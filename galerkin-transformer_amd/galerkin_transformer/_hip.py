@@ -105,6 +105,11 @@ _PROTOS = {
     "gt_galerkin_dkv_ln_ws_bytes": (C.c_int64, [C.c_int32] * 3),
     "gt_galerkin_dkv_ln_plain": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 5 + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]),
     "gt_galerkin_dkv_ln": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 5 + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]),
+    "gt_feature_softmax_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "gt_feature_softmax_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "gt_token_softmax_ws_bytes": (C.c_int64, [C.c_int32] * 5),
+    "gt_token_softmax_fwd": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_void_p, C.c_int64, C.c_void_p]),
+    "gt_token_softmax_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p, C.c_int64, C.c_void_p]),
     "gt_fourier_attn": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.POINTER(GtDropout),
                                                                 C.c_int32, C.c_void_p]),
     "gt_fourier16_image_bytes": (C.c_int64, [C.c_int32] * 4),
@@ -1171,6 +1176,60 @@ def galerkin_dkv_ln(Kp, Vp, dM, dQp, qkv, gamma, stats, B: int, n: int, h: int, 
                                                   dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws.numel(),
                                                   stream_ptr()), shape=(B, n, h, DP)), "gt_galerkin_dkv_ln")
     return d_qkv, dgamma, dbeta
+
+
+def linattn_supported(dk: int, p: int) -> bool:
+    """Head sizes of the 'linear' / 'global' softmax kernels: the head tiles the Galerkin path takes."""
+    return dk in (16, 32, 48, 64, 96) and 0 <= p <= 2
+
+
+def feature_softmax_fwd(X: torch.Tensor, rows: int, dk: int, p: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax over the dk + p columns of each of ``rows`` head-tile segments [rows, DP]; ``out=X`` runs in place."""
+    need_f32_cuda(X, out)
+    out = torch.empty_like(X) if out is None else out
+    DP = round4(dk + p)
+    check(_timed("gt_feature_softmax_fwd", 0, 8.0 * rows * DP,
+                 lambda: lib().gt_feature_softmax_fwd(X.data_ptr(), out.data_ptr(), rows, dk, p, stream_ptr()),
+                 shape=(rows, dk, p)), "gt_feature_softmax_fwd")
+    return out
+
+
+def feature_softmax_bwd(Y: torch.Tensor, dY: torch.Tensor, rows: int, dk: int, p: int,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dX = Y .* (dY - sum_c Y .* dY) per segment; ``out=dY`` runs in place."""
+    need_f32_cuda(Y, dY, out)
+    out = torch.empty_like(dY) if out is None else out
+    DP = round4(dk + p)
+    check(_timed("gt_feature_softmax_bwd", 0, 12.0 * rows * DP,
+                 lambda: lib().gt_feature_softmax_bwd(Y.data_ptr(), dY.data_ptr(), out.data_ptr(), rows, dk, p, stream_ptr()),
+                 shape=(rows, dk, p)), "gt_feature_softmax_bwd")
+    return out
+
+
+def token_softmax_fwd(X: torch.Tensor, B: int, n: int, h: int, dk: int, p: int,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax over the n tokens of every (batch, head, column < dk + p) of head tiles [B*n, h, DP]; ``out=X``: in place."""
+    need_f32_cuda(X, out)
+    out = torch.empty_like(X) if out is None else out
+    DP = round4(dk + p)
+    ws = workspace(X.device, max(16, lib().gt_token_softmax_ws_bytes(B, n, h, dk, p)))
+    check(_timed("gt_token_softmax_fwd", 0, 12.0 * B * n * h * DP,
+                 lambda: lib().gt_token_softmax_fwd(X.data_ptr(), out.data_ptr(), B, n, h, dk, p, ws.data_ptr(), ws.numel(),
+                                                    stream_ptr()), shape=(B, n, h, dk, p)), "gt_token_softmax_fwd")
+    return out
+
+
+def token_softmax_bwd(Y: torch.Tensor, dY: torch.Tensor, B: int, n: int, h: int, dk: int, p: int,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dX = Y .* (dY - sum_t Y .* dY) per column; ``out=dY`` runs in place."""
+    need_f32_cuda(Y, dY, out)
+    out = torch.empty_like(dY) if out is None else out
+    DP = round4(dk + p)
+    ws = workspace(Y.device, max(16, lib().gt_token_softmax_ws_bytes(B, n, h, dk, p)))
+    check(_timed("gt_token_softmax_bwd", 0, 20.0 * B * n * h * DP,
+                 lambda: lib().gt_token_softmax_bwd(Y.data_ptr(), dY.data_ptr(), out.data_ptr(), B, n, h, dk, p, ws.data_ptr(),
+                                                    ws.numel(), stream_ptr()), shape=(B, n, h, dk, p)), "gt_token_softmax_bwd")
+    return out
 
 
 def mlp_head_supported(K: int, N: int, n_out: int) -> bool:

@@ -28,7 +28,7 @@ def default(value, d):
 
 
 _LINEAR_FAMILY = ("linear", "galerkin", "global")
-_HIP_ATTENTION = ("galerkin", "fourier", "integral", "local")
+_HIP_ATTENTION = ("galerkin", "fourier", "integral", "local", "linear", "global")
 
 
 def _act_module(name, fallback="silu"):
@@ -419,7 +419,7 @@ class SimpleAttention(nn.Module):
         Fourier type run fused (no n x n matrix in HBM; the returned weight is None)."""
         if self.attention_type not in _HIP_ATTENTION:
             raise NotImplementedError(f"attention_type={self.attention_type!r} is outside the HIP hot path "
-                                      "(galerkin / fourier only)")
+                                      "(galerkin / fourier / linear only)")
         use_pos = pos is not None and self.pos_dim > 0
         if use_pos:
             assert pos.size(-1) == self.pos_dim
@@ -434,7 +434,12 @@ class SimpleAttention(nn.Module):
                 self._eye = (key, torch.eye(d, dtype=torch.float32, device=x.device))
             wfc, bfc = self._eye[1], None
         wqkv, bqkv, gamma, beta, mask = self._packed()
-        kind = "galerkin" if self.attention_type == "galerkin" else "fourier"
+        if self.attention_type == "galerkin":
+            kind = "galerkin"
+        elif self.attention_type in ("linear", "global"):     # the reference treats the two names alike (layers.py:719)
+            kind = "linear"
+        else:
+            kind = "fourier"
         out, w = ops.simple_attention(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc,
                                       kind=kind, n_head=self.n_head, norm_mask=mask, eps=self.eps,
                                       res=residual, sign=sign, p_out=p_out, need_weights=need_weights)

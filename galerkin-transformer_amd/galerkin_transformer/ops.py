@@ -1080,6 +1080,7 @@ class SimpleAttentionFn(Function):
     """out = res + sign * dropout1( fc( merge_heads( attention(Q', K', V') ) ) ).
 
     galerkin: per-head LN on K,V; M = mask .* (K'^T V')/n; heads: Q' M      (layers.py:708-734)
+    linear  : the same on Q~ = softmax(Q', dim=-1), K~ = softmax(K', dim=-2)  (layers.py:719-722; 'global' too)
     fourier : per-head LN on Q,K; S = mask .* (Q' K'^T)/sqrt(d_k')/n; heads: S V' (layers.py:672-705)
     with X' = [pos, X] per head (layers.py:869-874) and fc over the merged heads (layers.py:894-897).
     Also returns the attention matrix (``attn_weight``), detached."""
@@ -1087,6 +1088,8 @@ class SimpleAttentionFn(Function):
     @staticmethod
     def forward(ctx, x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, cfg, mask):
         (kind, h, norm_mask, eps, sign, p_attn, p_out, need_w) = cfg
+        if kind not in ("galerkin", "linear", "fourier"):
+            raise ValueError(f"simple_attention: kind={kind!r}")
         H.need_f32_cuda(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, mask)
         B, n, d = x.shape
         dk = d // h
@@ -1094,6 +1097,8 @@ class SimpleAttentionFn(Function):
         Dr, DP = dk + p, H.round4(dk + p)
         T = B * n
         dev = x.device
+        if kind == "linear" and not H.linattn_supported(dk, p):
+            raise H.GtNotSupported(f"linear attention: head size d_k={dk}, pos_dim={p} has no softmax kernel")
         xc = _c(x).reshape(T, d)
         posc = None if pos is None else _c(pos).reshape(T, p)
         wq, wf = _c(wqkv), _c(wfc)
@@ -1123,14 +1128,24 @@ class SimpleAttentionFn(Function):
             H.gemm(xc, wq, qkv, T, 3 * d, d, lda=d, ldb=d, ldc=3 * d, bias=bqkv, weight_b=True)
             out3, stats = H.headnorm_fwd(qkv, posc, gamma, beta, T, h, dk, p, norm_mask, eps)
         Qp, Kp, Vp = out3[0], out3[1], out3[2]
+        if kind == "linear":
+            # Q~ = softmax over the head's columns, K~ = softmax over the tokens, both in place: the backward needs the
+            # softmax outputs only, and the LayerNorm backward of K reads the raw projection, not the tiles
+            H.feature_softmax_fwd(Qp, T * h, dk, p, out=Qp)
+            H.token_softmax_fwd(Kp, B, n, h, dk, p, out=Kp)
         hD = h * DP
         out = torch.empty(T, d, dtype=torch.float32, device=dev)
         rc = None if res is None else _c(res).reshape(T, d)
         d_attn = H.dropout_desc(p_attn, salt, dev) if (p_attn > 0 and mask is None) else None
         d_out = H.dropout_desc(p_out, salt + 1, dev) if p_out > 0 else None
-        if kind == "galerkin":
-            slabs = H.galerkin_ktv(Kp, Vp, B, n, h, dk, p, gamma=gamma if plain else None,
-                                   beta=beta if plain else None)   # streaming MFMA kernel, token chunks
+        if kind in ("galerkin", "linear"):
+            slabs = None
+            if kind == "galerkin" or p == 0:
+                # (gt_galerkin_ktv reads the coordinate columns once, from K', for both operands: right for [pos, K], [pos, V],
+                # not for K~, whose coordinate columns went through the token softmax -- linear with coordinates contracts
+                # the full tiles through gt_gemm below)
+                slabs = H.galerkin_ktv(Kp, Vp, B, n, h, dk, p, gamma=gamma if plain else None,
+                                       beta=beta if plain else None)   # streaming MFMA kernel, token chunks
             if slabs is None:                                       # head sizes it does not cover
                 slabs = torch.empty(1, B, h, DP, DP, dtype=torch.float32, device=dev)
                 H.gemm(Kp, Vp, slabs, DP, DP, n, layout_a=1, layout_b=1, lda=hD, ldb=hD, ldc=DP, batch=(B, h),
@@ -1143,7 +1158,7 @@ class SimpleAttentionFn(Function):
             ctx.save_for_backward(xc, wq, gamma, wf, qkv, stats, out3, Mt, P, mask, beta if plain else None, Pv)
             ctx.plain = plain
             attn_w = Mt[:, :, :Dr, :Dr]
-        else:
+        elif kind == "fourier":
             scale = 1.0 / math.sqrt(Dr) / n
             wpad = torch.zeros(d, h, DP, dtype=torch.float32, device=dev)
             wpad[:, :, :Dr] = wf.reshape(d, h, Dr)
@@ -1204,7 +1219,7 @@ class SimpleAttentionFn(Function):
         fused_ln = False
         dO3 = None
         dbfc = None
-        if kind == "galerkin":
+        if kind in ("galerkin", "linear"):
             dbfc = torch.empty(d, dtype=torch.float32, device=dev) if hbf else None
             xc, wq, gamma, wf, qkv, stats, out3, Mt, P, mask, beta_plain, Pv = ctx.saved_tensors
             d_attn = H.dropout_desc(p_attn, salt, dev) if (p_attn > 0 and mask is None) else None
@@ -1217,7 +1232,8 @@ class SimpleAttentionFn(Function):
                        a_drop_sign=sign, a_drop_ld=d, a_drop_bstride=n * d, alpha=(sign if d_out is None else 1.0),
                        a_colsum=dbfc)       # + d(fc bias) = column sums of the masked, signed g
             # dQ'[b] = (sign*g*mask1)[b] P[b]^T
-            fused_ln = ctx.plain or (_dkv_ln_fused[0] and H.galerkin_dkv_ln_supported(dk, p, norm_mask))
+            # (linear: the softmax backwards sit between dK' and the LayerNorm backward, so the fused kernel does not apply)
+            fused_ln = kind == "galerkin" and (ctx.plain or (_dkv_ln_fused[0] and H.galerkin_dkv_ln_supported(dk, p, norm_mask)))
             if fused_ln:
                 # only the value columns of dQ' reach d_qkv (the coordinates take no gradient): contract with those rows
                 # of P and write the Q block of d_qkv directly -- one 128-wide tile column instead of h*DP = 144, no
@@ -1246,7 +1262,11 @@ class SimpleAttentionFn(Function):
                        b_bs=(h * DP * DP, DP * DP), c_bs=(n * hD, DP))
                 H.gemm(Kp, dM, dO3[2], n, DP, DP, layout_b=1, lda=hD, ldb=DP, ldc=hD, batch=(B, h),
                        a_bs=(n * hD, DP), b_bs=(h * DP * DP, DP * DP), c_bs=(n * hD, DP))
-        else:
+            if kind == "linear":
+                # Qp, Kp hold Q~, K~: dQ' = Q~ .* (dQ~ - sum_c Q~ dQ~), dK' = K~ .* (dK~ - sum_t K~ dK~), in place
+                H.feature_softmax_bwd(Qp, dO3[0], T * h, dk, p, out=dO3[0])
+                H.token_softmax_bwd(Kp, dO3[1], B, n, h, dk, p, out=dO3[1])
+        elif kind == "fourier":
             xc, wq, gamma, wpad, qkv, stats, out3, S, att, mask = ctx.saved_tensors
             dO3 = torch.empty(3, T, h, DP, dtype=torch.float32, device=dev)
             d_attn = H.dropout_desc(p_attn, salt, dev) if (p_attn > 0 and mask is None) else None
@@ -1291,7 +1311,7 @@ class SimpleAttentionFn(Function):
                        a_bs=(h * n * n, n * n), b_bs=(n * hD, DP), c_bs=(n * hD, DP))
                 H.gemm(dS, Qp, dO3[1], n, DP, n, layout_a=1, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h),
                        a_bs=(h * n * n, n * n), b_bs=(n * hD, DP), c_bs=(n * hD, DP))
-        if not (kind == "galerkin" and fused_ln):
+        if not fused_ln:
             dqkv, dgamma, dbeta = H.headnorm_bwd(dO3, qkv, gamma, stats, T, h, dk, p, norm_mask)
         dwqkv = torch.empty(3 * d, d, dtype=torch.float32, device=dev)
         dbqkv = torch.empty(3 * d, dtype=torch.float32, device=dev) if hbq else None
@@ -1328,7 +1348,7 @@ def simple_attention(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, *, kind: str, n_
         if not _attn_masks:
             raise RuntimeError("attention dropout mode 'replay' but no mask queued")
         m = _attn_masks.pop(0).to(device=x.device, dtype=torch.float32)
-        if kind == "galerkin":
+        if kind in ("galerkin", "linear"):
             Dr = m.shape[-1]
             DP = H.round4(Dr)
             mask = torch.zeros(*m.shape[:2], DP, DP, dtype=torch.float32, device=x.device)

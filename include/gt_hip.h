@@ -389,6 +389,31 @@ int gt_galerkin_dkv_ln_plain(const float* Kp, const float* Vp, const float* dM, 
                              void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The softmax pair of the 'linear' / 'global' attention family (layers.py:719-722; ABI v21, additive):
+ *     Q~ = softmax(Q', dim=-1)  over the Dr = dk + p columns of every (token, head)      -- "feature" softmax
+ *     K~ = softmax(K', dim=-2)  over the n tokens of every (batch, head, column < Dr)    -- "token" softmax
+ * on the head-tile layout [B*n][h][DP], DP = round4(Dr), that gt_headnorm_fwd writes.  The coordinate columns take part,
+ * the pad columns Dr..DP-1 do not and are written as exact zeros.  The rest of the family is the Galerkin path on
+ * (Q~, K~, V'): gt_galerkin_ktv, the finalize pair, the Q~ P product, gt_galerkin_dkv.
+ *     feature softmax: rows = B*n*h segments of DP floats; one pass forward, one backward
+ *                      dX = Y .* (dY - sum_c Y .* dY)   from the OUTPUT Y (Q' is not needed)
+ *     token softmax:   a statistics pass (running max / sum per column and chunk of 128 tokens, partials in ws) and an
+ *                      applying pass that merges the partials in a fixed order; the backward likewise:
+ *                      c = sum_t Y .* dY per column,  dX = Y .* (dY - c).   ws >= the ws_bytes query.
+ * The row maximum is subtracted before every exponential; no atomics: results are bit-identical from run to run.
+ * In place is allowed (Y == X; dX == dY).  fp32 in every precision mode.
+ * dk in {16, 32, 48, 64, 96} and p in {0, 1, 2} (the head tiles of the Galerkin path), any n >= 1; else GT_ENOTSUP.
+ * ------------------------------------------------------------------------------------------- */
+int gt_feature_softmax_fwd(const float* X, float* Y, int64_t rows, int32_t dk, int32_t p, void* stream);
+int gt_feature_softmax_bwd(const float* Y, const float* dY, float* dX, int64_t rows, int32_t dk, int32_t p,
+                           void* stream);
+int64_t gt_token_softmax_ws_bytes(int32_t B, int32_t n, int32_t h, int32_t dk, int32_t p);
+int gt_token_softmax_fwd(const float* X, float* Y, int32_t B, int32_t n, int32_t h, int32_t dk, int32_t p,
+                         void* ws, int64_t ws_bytes, void* stream);
+int gt_token_softmax_bwd(const float* Y, const float* dY, float* dX, int32_t B, int32_t n, int32_t h, int32_t dk,
+                         int32_t p, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused Fourier-type attention (layers.py:672-705):  out = ((Q' K'^T) * scale .* mask) V'  on the head-tile
  * layout [B*n][h][DP], without writing the n x n score matrix: score tiles are scaled, masked (stateless
  * dropout with mask index ((b*h+head)*n + query)*n + key -- the index the materialising gt_gemm path uses --

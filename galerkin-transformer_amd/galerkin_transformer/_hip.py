@@ -110,6 +110,10 @@ _PROTOS = {
     "gt_token_softmax_ws_bytes": (C.c_int64, [C.c_int32] * 5),
     "gt_token_softmax_fwd": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_void_p, C.c_int64, C.c_void_p]),
     "gt_token_softmax_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p, C.c_int64, C.c_void_p]),
+    "gt_token_norm_ws_bytes": (C.c_int64, [C.c_int32] * 5),
+    "gt_token_norm_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 2 + [C.c_int32] * 5
+                          + [C.c_void_p, C.c_int64, C.c_void_p]),
+    "gt_token_norm_bwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 5 + [C.c_void_p, C.c_int64, C.c_void_p]),
     "gt_fourier_attn": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.POINTER(GtDropout),
                                                                 C.c_int32, C.c_void_p]),
     "gt_fourier16_image_bytes": (C.c_int64, [C.c_int32] * 4),
@@ -1230,6 +1234,42 @@ def token_softmax_bwd(Y: torch.Tensor, dY: torch.Tensor, B: int, n: int, h: int,
                  lambda: lib().gt_token_softmax_bwd(Y.data_ptr(), dY.data_ptr(), out.data_ptr(), B, n, h, dk, p, ws.data_ptr(),
                                                     ws.numel(), stream_ptr()), shape=(B, n, h, dk, p)), "gt_token_softmax_bwd")
     return out
+
+
+def token_norm_fwd(X: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, B: int, n: int, h: int, dk: int,
+                   p: int, out: Optional[torch.Tensor] = None):
+    """Token-axis (instance) norm of the value columns of head tiles [B*n, h, DP]; gamma, beta [h, dk].  Returns
+    (Y, stats [B, h, dk, 2] = (mean, rstd)); ``out=X`` runs in place."""
+    need_f32_cuda(X, gamma, beta, out)
+    out = torch.empty_like(X) if out is None else out
+    DP = round4(dk + p)
+    stats = torch.empty(B, h, dk, 2, dtype=torch.float32, device=X.device)
+    ws = workspace(X.device, max(16, lib().gt_token_norm_ws_bytes(B, n, h, dk, p)))
+    check(_timed("gt_token_norm_fwd", 0, 12.0 * B * n * h * DP,
+                 lambda: lib().gt_token_norm_fwd(X.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), out.data_ptr(),
+                                                 stats.data_ptr(), B, n, h, dk, p, ws.data_ptr(), ws.numel(), stream_ptr()),
+                 shape=(B, n, h, dk, p)), "gt_token_norm_fwd")
+    return out, stats
+
+
+def token_norm_bwd(X: torch.Tensor, dY: torch.Tensor, gamma: torch.Tensor, stats: torch.Tensor, B: int, n: int, h: int,
+                   dk: int, p: int, out: Optional[torch.Tensor] = None, dgamma: Optional[torch.Tensor] = None,
+                   dbeta: Optional[torch.Tensor] = None):
+    """Backward of token_norm_fwd from the RAW tiles X and the forward's stats.  Returns (dX, dgamma, dbeta [h, dk]);
+    ``out=dY`` runs in place, ``dgamma`` / ``dbeta`` may be views to fill."""
+    need_f32_cuda(X, dY, gamma, stats, out, dgamma, dbeta)
+    out = torch.empty_like(dY) if out is None else out
+    dgamma = torch.empty(h, dk, dtype=torch.float32, device=X.device) if dgamma is None else dgamma
+    dbeta = torch.empty(h, dk, dtype=torch.float32, device=X.device) if dbeta is None else dbeta
+    if not (dgamma.is_contiguous() and dbeta.is_contiguous()):
+        raise ValueError("token_norm_bwd: dgamma / dbeta must be contiguous")
+    DP = round4(dk + p)
+    ws = workspace(X.device, max(16, lib().gt_token_norm_ws_bytes(B, n, h, dk, p)))
+    check(_timed("gt_token_norm_bwd", 0, 20.0 * B * n * h * DP,
+                 lambda: lib().gt_token_norm_bwd(X.data_ptr(), dY.data_ptr(), gamma.data_ptr(), stats.data_ptr(), out.data_ptr(),
+                                                 dgamma.data_ptr(), dbeta.data_ptr(), B, n, h, dk, p, ws.data_ptr(), ws.numel(),
+                                                 stream_ptr()), shape=(B, n, h, dk, p)), "gt_token_norm_bwd")
+    return out, dgamma, dbeta
 
 
 def mlp_head_supported(K: int, N: int, n_out: int) -> bool:

@@ -332,8 +332,11 @@ class SimpleAttention(nn.Module):
 
     Same parameters / state_dict keys as the reference (layers.py:793-828): ``linears.{0,1,2}``,
     ``norm_K.{i}``, ``norm_V.{i}`` (galerkin) or ``norm_Q.{i}`` (fourier), ``fc``.  The HIP path covers
-    self-attention (query is key is value) of the 'galerkin' and 'fourier' ('integral', 'local') types
-    with norm_type='layer'; other variants of the reference are baselines outside the hot path."""
+    self-attention (query is key is value) of the 'galerkin', 'linear' / 'global' and 'fourier' ('integral', 'local')
+    types with norm_type='layer', and the Galerkin family with norm_type='instance': ``norm_K`` / ``norm_V`` are then
+    ``nn.InstanceNorm1d(d_k, affine=True)`` per head (same keys and shapes, no buffers) and K, V are normalised over the
+    tokens, one mean and variance per (sample, head, channel), before the coordinates are concatenated (layers.py:842-854).
+    Other variants of the reference are baselines outside the hot path."""
 
     def __init__(self, n_head, d_model, pos_dim: int = 1, attention_type="fourier", dropout=0.1,
                  xavier_init=1e-4, diagonal_weight=1e-2, symmetric_init=False, norm=False,
@@ -374,10 +377,17 @@ class SimpleAttention(nn.Module):
                 constant_(param, 0)
 
     def _get_norm(self, eps):
-        if self.norm_type != "layer":
-            raise NotImplementedError("only norm_type='layer' has a HIP path (the reference's 'instance' "
-                                      "branch is unused by its configs)")
-        mk = lambda: nn.ModuleList([nn.LayerNorm(self.d_k, eps=eps) for _ in range(self.n_head)])
+        if self.norm_type == "instance":
+            if self.attention_type not in _LINEAR_FAMILY:
+                # layers.py:867 assigns the transposed VALUE to `query`; the coordinate concatenation then fails on the sizes
+                raise NotImplementedError(f"norm_type='instance' with attention_type={self.attention_type!r}: that branch of "
+                                          "the reference does not run (layers.py:867 mixes up query and value), so there "
+                                          "are no semantics to match; 'instance' covers galerkin / linear / global")
+            mk = lambda: nn.ModuleList([nn.InstanceNorm1d(self.d_k, eps=eps, affine=True) for _ in range(self.n_head)])
+        elif self.norm_type == "layer":
+            mk = lambda: nn.ModuleList([nn.LayerNorm(self.d_k, eps=eps) for _ in range(self.n_head)])
+        else:
+            raise NotImplementedError(f"norm_type={self.norm_type!r}: 'layer' and 'instance' have a HIP path")
         self.norm_K = mk()
         if self.attention_type in _LINEAR_FAMILY:
             self.norm_V = mk()
@@ -442,7 +452,8 @@ class SimpleAttention(nn.Module):
             kind = "fourier"
         out, w = ops.simple_attention(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc,
                                       kind=kind, n_head=self.n_head, norm_mask=mask, eps=self.eps,
-                                      res=residual, sign=sign, p_out=p_out, need_weights=need_weights)
+                                      res=residual, sign=sign, p_out=p_out, need_weights=need_weights,
+                                      token_norm=self.add_norm and self.norm_type == "instance")
         self.attn_weight = w
         return out, w
 

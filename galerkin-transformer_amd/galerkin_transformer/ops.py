@@ -1083,13 +1083,17 @@ class SimpleAttentionFn(Function):
     linear  : the same on Q~ = softmax(Q', dim=-1), K~ = softmax(K', dim=-2)  (layers.py:719-722; 'global' too)
     fourier : per-head LN on Q,K; S = mask .* (Q' K'^T)/sqrt(d_k')/n; heads: S V' (layers.py:672-705)
     with X' = [pos, X] per head (layers.py:869-874) and fc over the merged heads (layers.py:894-897).
+    token_norm (norm_type='instance', galerkin / linear): K, V are normalised over the TOKENS per (sample, head, channel)
+    instead (layers.py:842-854): the projection writes raw tiles, gt_token_norm_fwd normalises their value columns.
     Also returns the attention matrix (``attn_weight``), detached."""
 
     @staticmethod
     def forward(ctx, x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, cfg, mask):
-        (kind, h, norm_mask, eps, sign, p_attn, p_out, need_w) = cfg
+        (kind, h, norm_mask, eps, sign, p_attn, p_out, need_w, token_norm) = cfg
         if kind not in ("galerkin", "linear", "fourier"):
             raise ValueError(f"simple_attention: kind={kind!r}")
+        if token_norm and (kind == "fourier" or norm_mask != 0b110 or gamma is None or beta is None):
+            raise ValueError("simple_attention: token_norm is the K, V norm of the galerkin / linear kinds")
         H.need_f32_cuda(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, mask)
         B, n, d = x.shape
         dk = d // h
@@ -1099,6 +1103,15 @@ class SimpleAttentionFn(Function):
         dev = x.device
         if kind == "linear" and not H.linattn_supported(dk, p):
             raise H.GtNotSupported(f"linear attention: head size d_k={dk}, pos_dim={p} has no softmax kernel")
+        if token_norm:
+            if n < 2:       # nn.InstanceNorm1d: "Expected more than 1 spatial element when training"
+                raise ValueError(f"norm_type='instance' needs more than 1 token per sample to normalise over (got n={n})")
+            if not H.linattn_supported(dk, p):
+                raise H.GtNotSupported(f"norm_type='instance': head size d_k={dk}, pos_dim={p} has no token-norm kernel")
+            # the projection leaves RAW K, V (+ coordinates) in the tiles: no per-token norm, no affine on its epilogue
+            hn_mask, hn_gamma, hn_beta = 0, None, None
+        else:
+            hn_mask, hn_gamma, hn_beta = norm_mask, gamma, beta
         xc = _c(x).reshape(T, d)
         posc = None if pos is None else _c(pos).reshape(T, p)
         wq, wf = _c(wqkv), _c(wfc)
@@ -1108,26 +1121,37 @@ class SimpleAttentionFn(Function):
         # normalised values WITHOUT the LayerNorm affine (the consumers apply gamma / beta), the backward takes xh from the
         # tiles, and the raw projection has no reader left: it is neither written nor allocated (gt_hip.h: hn_plain)
         plain = (_plain_tiles[0] and kind == "galerkin" and _dkv_ln_fused[0] and H.galerkin_dkv_ln_supported(dk, p, norm_mask)
-                 and H.galerkin_ktv_supported(dk, p))
+                 and H.galerkin_ktv_supported(dk, p) and not token_norm)
         if _qkvnorm_fused[0] and dk in (16, 32, 48, 64) and bqkv is not None and H.get_precision() in H.SPLIT_EXACT:
             # head norm on the projection's epilogue (GT_EP_HEADNORM): one pass less over [T, 3d], one launch less
             out3 = torch.empty(3, T, h, DP, dtype=torch.float32, device=dev)
             stats = torch.empty(2, T, h, 2, dtype=torch.float32, device=dev)
-            if not plain:
+            if not plain and not token_norm:       # (token_norm: no stream is LayerNormed, nothing reads the raw projection)
                 qkv = torch.empty(T, 3 * d, dtype=torch.float32, device=dev)
             try:
                 # the raw projection is kept for the LayerNorm backward only: the normalised streams' blocks of qkv
                 H.gemm(xc, wq, qkv, T, 3 * d, d, lda=d, ldb=d, ldc=3 * d, bias=bqkv, weight_b=True,
-                       hn=dict(gamma=gamma, beta=beta, pos=posc, out=out3, stats=stats, h=h, dk=dk, p=p,
-                               norm_mask=norm_mask, eps=eps, skip_raw=7 if plain else (~norm_mask) & 7, plain=plain))
+                       hn=dict(gamma=hn_gamma, beta=hn_beta, pos=posc, out=out3, stats=stats, h=h, dk=dk, p=p,
+                               norm_mask=hn_mask, eps=eps, skip_raw=7 if plain else (~hn_mask) & 7, plain=plain))
             except H.GtNotSupported:                          # shapes / alignment the fused kernel does not take
                 out3 = None
         if out3 is None:
             plain = False
             qkv = torch.empty(T, 3 * d, dtype=torch.float32, device=dev)
             H.gemm(xc, wq, qkv, T, 3 * d, d, lda=d, ldb=d, ldc=3 * d, bias=bqkv, weight_b=True)
-            out3, stats = H.headnorm_fwd(qkv, posc, gamma, beta, T, h, dk, p, norm_mask, eps)
+            out3, stats = H.headnorm_fwd(qkv, posc, hn_gamma, hn_beta, T, h, dk, p, hn_mask, eps)
+            if token_norm:
+                qkv = None
         Qp, Kp, Vp = out3[0], out3[1], out3[2]
+        tn_saved = ()
+        if token_norm:
+            # out3[1:] keep the raw tiles for the backward (xh is recomputed from them: a zero weight must work); the
+            # normalised pair goes to its own buffer, which the softmax / contraction chain below reads and rewrites
+            kvn = torch.empty(2, T, h, DP, dtype=torch.float32, device=dev)
+            _, st_k = H.token_norm_fwd(out3[1], gamma[0], beta[0], eps, B, n, h, dk, p, out=kvn[0])
+            _, st_v = H.token_norm_fwd(out3[2], gamma[1], beta[1], eps, B, n, h, dk, p, out=kvn[1])
+            Kp, Vp = kvn[0], kvn[1]
+            tn_saved = (kvn, st_k, st_v)
         if kind == "linear":
             # Q~ = softmax over the head's columns, K~ = softmax over the tokens, both in place: the backward needs the
             # softmax outputs only, and the LayerNorm backward of K reads the raw projection, not the tiles
@@ -1155,7 +1179,7 @@ class SimpleAttentionFn(Function):
             H.gemm(Qp, P, out, n, d, hD, layout_b=1, lda=hD, ldb=d, ldc=d, batch=(B, 1), a_bs=(n * hD, 0),
                    b_bs=(hD * d, 0), c_bs=(n * d, 0), bias=bfc, drop=d_out, res=rc, ldr=d, r_bs=(n * d, 0),
                    out_scale=sign)
-            ctx.save_for_backward(xc, wq, gamma, wf, qkv, stats, out3, Mt, P, mask, beta if plain else None, Pv)
+            ctx.save_for_backward(xc, wq, gamma, wf, qkv, stats, out3, Mt, P, mask, beta if plain else None, Pv, *tn_saved)
             ctx.plain = plain
             attn_w = Mt[:, :, :Dr, :Dr]
         elif kind == "fourier":
@@ -1206,7 +1230,7 @@ class SimpleAttentionFn(Function):
 
     @staticmethod
     def backward(ctx, gy, _gw):
-        (kind, h, norm_mask, eps, sign, p_attn, p_out, need_w) = ctx.cfg
+        (kind, h, norm_mask, eps, sign, p_attn, p_out, need_w, token_norm) = ctx.cfg
         B, n, d, h, dk, p, Dr, DP, salt, hbq, hbf, has_res, xshape = ctx.dims
         T, hD = B * n, h * DP
         dev = gy.device
@@ -1221,9 +1245,12 @@ class SimpleAttentionFn(Function):
         dbfc = None
         if kind in ("galerkin", "linear"):
             dbfc = torch.empty(d, dtype=torch.float32, device=dev) if hbf else None
-            xc, wq, gamma, wf, qkv, stats, out3, Mt, P, mask, beta_plain, Pv = ctx.saved_tensors
+            xc, wq, gamma, wf, qkv, stats, out3, Mt, P, mask, beta_plain, Pv = ctx.saved_tensors[:12]
             d_attn = H.dropout_desc(p_attn, salt, dev) if (p_attn > 0 and mask is None) else None
             Qp, Kp, Vp = out3[0], out3[1], out3[2]
+            if token_norm:      # the contractions ran on the normalised pair; out3[1:] are the raw tiles
+                kvn, st_k, st_v = ctx.saved_tensors[12:]
+                Kp, Vp = kvn[0], kvn[1]
             # dP^T[b] = (sign*g*mask1)^T[b] Q'[b]        [B, d, h*DP]
             dPt = torch.empty(B, d, hD, dtype=torch.float32, device=dev)
             with H.side_branch(dev, T): # the token-contracted product next to the token-row product below
@@ -1233,7 +1260,8 @@ class SimpleAttentionFn(Function):
                        a_colsum=dbfc)       # + d(fc bias) = column sums of the masked, signed g
             # dQ'[b] = (sign*g*mask1)[b] P[b]^T
             # (linear: the softmax backwards sit between dK' and the LayerNorm backward, so the fused kernel does not apply)
-            fused_ln = kind == "galerkin" and (ctx.plain or (_dkv_ln_fused[0] and H.galerkin_dkv_ln_supported(dk, p, norm_mask)))
+            fused_ln = (kind == "galerkin" and not token_norm
+                        and (ctx.plain or (_dkv_ln_fused[0] and H.galerkin_dkv_ln_supported(dk, p, norm_mask))))
             if fused_ln:
                 # only the value columns of dQ' reach d_qkv (the coordinates take no gradient): contract with those rows
                 # of P and write the Q block of d_qkv directly -- one 128-wide tile column instead of h*DP = 144, no
@@ -1266,6 +1294,12 @@ class SimpleAttentionFn(Function):
                 # Qp, Kp hold Q~, K~: dQ' = Q~ .* (dQ~ - sum_c Q~ dQ~), dK' = K~ .* (dK~ - sum_t K~ dK~), in place
                 H.feature_softmax_bwd(Qp, dO3[0], T * h, dk, p, out=dO3[0])
                 H.token_softmax_bwd(Kp, dO3[1], B, n, h, dk, p, out=dO3[1])
+            if token_norm:
+                # dK', dV' -> gradients of the raw tiles, in place; the affine gradients in (norm_K, norm_V) order
+                dgamma = torch.empty(2, h, dk, dtype=torch.float32, device=dev)
+                dbeta = torch.empty(2, h, dk, dtype=torch.float32, device=dev)
+                H.token_norm_bwd(out3[1], dO3[1], gamma[0], st_k, B, n, h, dk, p, out=dO3[1], dgamma=dgamma[0], dbeta=dbeta[0])
+                H.token_norm_bwd(out3[2], dO3[2], gamma[1], st_v, B, n, h, dk, p, out=dO3[2], dgamma=dgamma[1], dbeta=dbeta[1])
         elif kind == "fourier":
             xc, wq, gamma, wpad, qkv, stats, out3, S, att, mask = ctx.saved_tensors
             dO3 = torch.empty(3, T, h, DP, dtype=torch.float32, device=dev)
@@ -1311,7 +1345,11 @@ class SimpleAttentionFn(Function):
                        a_bs=(h * n * n, n * n), b_bs=(n * hD, DP), c_bs=(n * hD, DP))
                 H.gemm(dS, Qp, dO3[1], n, DP, n, layout_a=1, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h),
                        a_bs=(h * n * n, n * n), b_bs=(n * hD, DP), c_bs=(n * hD, DP))
-        if not fused_ln:
+        if token_norm:
+            # scatter only: the value columns of the three gradient tiles into d_qkv (no stream is LayerNormed, so the raw
+            # projection is not read; where the forward did not keep one, the gradient tiles stand in for the pointer)
+            dqkv, _, _ = H.headnorm_bwd(dO3, qkv if qkv is not None else dO3, None, stats, T, h, dk, p, 0)
+        elif not fused_ln:
             dqkv, dgamma, dbeta = H.headnorm_bwd(dO3, qkv, gamma, stats, T, h, dk, p, norm_mask)
         dwqkv = torch.empty(3 * d, d, dtype=torch.float32, device=dev)
         dbqkv = torch.empty(3 * d, dtype=torch.float32, device=dev) if hbq else None
@@ -1335,10 +1373,12 @@ class SimpleAttentionFn(Function):
 
 
 def simple_attention(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, *, kind: str, n_head: int, norm_mask: int,
-                     eps: float, res=None, sign: float = 1.0, p_out: float = 0.0, need_weights: bool = True):
+                     eps: float, res=None, sign: float = 1.0, p_out: float = 0.0, need_weights: bool = True,
+                     token_norm: bool = False):
     """Self-attention block; ``res`` must be ``x`` (or None).  Returns (out, attn_weight).  For the Fourier
     type ``need_weights=False`` selects the fused kernel that never materialises the n x n matrix
-    (attn_weight is then None); the Galerkin matrix is small and always returned."""
+    (attn_weight is then None); the Galerkin matrix is small and always returned.  ``token_norm`` (galerkin / linear with
+    norm_mask = K, V): gamma / beta are the affine of the token-axis norm (norm_type='instance') instead of the LayerNorm's."""
     _check_res_is_x(res, x, "simple_attention")
     mode = _attn_mode
     mask, p_attn = None, 0.0
@@ -1356,6 +1396,6 @@ def simple_attention(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, *, kind: str, n_
         else:
             mask = _c(m)
     cfg = (kind, int(n_head), int(norm_mask), float(eps), float(sign), float(p_attn), float(p_out),
-           bool(need_weights))
+           bool(need_weights), bool(token_norm))
     out, w = SimpleAttentionFn.apply(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, cfg, mask)
     return out, (w if w.numel() else None)

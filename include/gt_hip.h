@@ -414,6 +414,29 @@ int gt_token_softmax_bwd(const float* Y, const float* dY, float* dX, int32_t B, 
                          int32_t p, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Token-axis ("instance") norm of a K or V head tile: norm_type='instance' of the Galerkin family (layers.py:842-854,
+ * nn.InstanceNorm1d(d_k, affine=True) per head; ABI v21, additive).  For every (sample, head, value channel c):
+ *     y[t] = (x[t] - mean_t x) * rstd * gamma[head][c] + beta[head][c],   rstd = 1 / sqrt(biased var_t x + eps)
+ * over the n tokens, on the head-tile layout [B*n][h][DP], DP = round4(dk + p).  The p coordinate columns are copied
+ * through, the pad columns are written as exact zeros (forward and backward).  gamma, beta, dgamma, dbeta: [h][dk];
+ * stats [B][h][dk][2] = (mean, rstd), written by the forward and read by the backward.
+ *     forward : per-chunk Welford (mean, M2) partials in ws, merged in chunk order with the pairwise update (never
+ *               E[x^2] - mean^2), then the applying pass
+ *     backward: xh = (x - mean) rstd from the RAW input X and stats (never Y / gamma: a zero weight is legal);
+ *               dX = rstd gamma (dY - mean_t dY - xh mean_t(dY xh)),  dgamma = sum_{b,t} dY xh,  dbeta = sum_{b,t} dY,
+ *               chunks, then samples, summed in order.  dgamma / dbeta may be NULL (not wanted).
+ * No atomics: bit-identical from run to run.  In place is allowed (Y == X; dX == dY).  fp32 in every precision mode.
+ * dk in {16, 32, 48, 64, 96} and p in {0, 1, 2}, else GT_ENOTSUP (the ws query returns 0); the forward refuses n == 1
+ * (GT_EINVAL).  ws >= gt_token_norm_ws_bytes, which serves both directions.
+ * ------------------------------------------------------------------------------------------- */
+int64_t gt_token_norm_ws_bytes(int32_t B, int32_t n, int32_t h, int32_t dk, int32_t p);
+int gt_token_norm_fwd(const float* X, const float* gamma, const float* beta, float eps, float* Y, float* stats,
+                      int32_t B, int32_t n, int32_t h, int32_t dk, int32_t p, void* ws, int64_t ws_bytes, void* stream);
+int gt_token_norm_bwd(const float* X, const float* dY, const float* gamma, const float* stats, float* dX,
+                      float* dgamma, float* dbeta, int32_t B, int32_t n, int32_t h, int32_t dk, int32_t p, void* ws,
+                      int64_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused Fourier-type attention (layers.py:672-705):  out = ((Q' K'^T) * scale .* mask) V'  on the head-tile
  * layout [B*n][h][DP], without writing the n x n score matrix: score tiles are scaled, masked (stateless
  * dropout with mask index ((b*h+head)*n + query)*n + key -- the index the materialising gt_gemm path uses --

@@ -183,8 +183,21 @@ enum { F16_PLAIN = 0, F16_DROP = 1, F16_DROPH = 2, F16_MASK = 3, F16_DROPB = 4 }
 // go L2 -> LDS by direct loads and that path saturates near 6.4 TB/s for the chip (MI355X_MICROARCH.md: ldsdma-fill); with
 // 128 owners per tile the C3 passes asked for 4.4 - 5.3 TB/s of it (1.24 GB per launch) and did not get faster without the
 // dropout hash, with 256 owners for half of that.
+//
+// Waves per SIMD an instance is compiled for: the register budget is 512 / waves per lane, VGPR + AGPR together.  A wave holds
+// the owner fragments (16 NS registers, twice that in the dual pass) and the accumulators (8 ND, twice) before any temporary:
+// 88 at DP = 68 and 120 at DP = 100 single, 176 / 240 dual.  The dual pass at DP = 100 takes the whole register file (one wave
+// per SIMD = one 4-wave block per CU, whose 108 KiB stage leaves room for no second block anyway); the one at DP = 68 would too,
+// and is not built (f16_split_dual below).  The wide single passes get 256 registers: DP = 100 needs 176 - 239 of them; DP = 68 comes out at 148 - 165, which still runs 3 waves per SIMD, where
+// a budget of 168 made the two per-element dropout instances spill.  DESIGN 4.3 has the compiler's figures for every instance.
+template <int DP, bool DUAL, int NW>
+constexpr int f16_waves_per_simd() {
+    if (DP > 52) return DUAL ? 1 : 2;
+    return DUAL ? 2 : (DP > 36 ? 3 : 4);
+}
+
 template <int DP, bool DUAL, int MODE, int NW>
-__global__ __launch_bounds__(64 * NW, DUAL ? 2 : (DP > 36 ? 3 : 4)) void fourier16_kernel(const F16P p) {
+__global__ __launch_bounds__(64 * NW, (f16_waves_per_simd<DP, DUAL, NW>())) void fourier16_kernel(const F16P p) {
     using G = F16G<DP>;
     constexpr int NM = G::NM, TG = G::TG, NS = G::NS, ND = G::ND;
     constexpr int STAGE = DUAL ? 2 * G::IMG : G::IMG;            // one image of each stream tensor / T1's rm + T2's tr
@@ -525,6 +538,15 @@ __global__ __launch_bounds__(64 * NW, DUAL ? 2 : (DP > 36 ? 3 : 4)) void fourier
     }
 }
 
+// The dual pass computes exactly what two single-output passes over the same owners compute -- O1 from (F1; T1, T2), O2 from
+// (F2; T2, T1), bit for bit: the same products in the same order under the same running exponents -- and shares the stream
+// tiles between them.  At DP = 68 it is run as those two passes: the dual instance needs 320 - 352 registers, i.e. one wave per
+// SIMD, and took 0.61 ms at (B, n, h) = (8, 3721, 2) where the two single passes (3 waves per SIMD) take 0.40 together; at
+// DP = 100 the two ways measured the same (0.77 / 0.79 ms at (4, 8192, 1), 0.21 / 0.21 at (8, 2048, 1)) and the dual instance,
+// with one launch and one trip of the images, stays.  DESIGN 4.3.
+template <int DP>
+constexpr bool f16_split_dual() { return DP == 68; }
+
 template <int DP, int NW>
 static void fourier16_launch_nw(const F16P& p, bool dual, bool block16, hipStream_t st) {
     int mode = F16_PLAIN;
@@ -533,11 +555,14 @@ static void fourier16_launch_nw(const F16P& p, bool dual, bool block16, hipStrea
     const dim3 grid((unsigned)p.total);
 #define GT_F16(D, M) hipLaunchKernelGGL((fourier16_kernel<DP, D, M, NW>), grid, dim3(64 * NW), 0, st, p)
     if (dual) {
-        if (mode == F16_DROPB) GT_F16(true, F16_DROPB);
-        else if (mode == F16_DROPH) GT_F16(true, F16_DROPH);
-        else if (mode == F16_DROP) GT_F16(true, F16_DROP);
-        else if (mode == F16_MASK) GT_F16(true, F16_MASK);
-        else GT_F16(true, F16_PLAIN);
+        // (a wide dual pass exists with 4 waves per block only -- f16_pick_nw -- and not at all where it is split)
+        if constexpr (!f16_split_dual<DP>() && (DP <= 52 || NW == 4)) {
+            if (mode == F16_DROPB) GT_F16(true, F16_DROPB);
+            else if (mode == F16_DROPH) GT_F16(true, F16_DROPH);
+            else if (mode == F16_DROP) GT_F16(true, F16_DROP);
+            else if (mode == F16_MASK) GT_F16(true, F16_MASK);
+            else GT_F16(true, F16_PLAIN);
+        }
     } else {
         if (mode == F16_DROPB) GT_F16(false, F16_DROPB);
         else if (mode == F16_DROPH) GT_F16(false, F16_DROPH);
@@ -557,6 +582,16 @@ static int f16_pick_nw(int64_t BH, int ntile, bool dual) {
 
 template <int DP>
 static void fourier16_launch(F16P& p, bool dual, bool block16, int64_t BH, hipStream_t st) {
+    if constexpr (f16_split_dual<DP>()) {
+        if (dual) {
+            F16P a = p, b = p;
+            a.F2 = nullptr; a.O2 = nullptr;
+            b.F1 = p.F2; b.F2 = nullptr; b.T1 = p.T2; b.T2 = p.T1; b.O1 = p.O2; b.O2 = nullptr;
+            fourier16_launch<DP>(a, false, block16, BH, st);
+            fourier16_launch<DP>(b, false, block16, BH, st);
+            return;
+        }
+    }
     const int nw = f16_pick_nw(BH, p.ntile, dual);
     p.nblk = ceil_div(p.ntile, nw);
     p.total = (int)(BH * p.nblk);
@@ -570,6 +605,8 @@ static int f16_img_bytes(int DP) {
         case 20: return F16G<20>::IMG;
         case 36: return F16G<36>::IMG;
         case 52: return F16G<52>::IMG;
+        case 68: return F16G<68>::IMG;
+        case 100: return F16G<100>::IMG;
         default: return 0;
     }
 }
@@ -637,7 +674,10 @@ extern "C" int gt_fourier16_presplit(const float* X0, const float* X1, const flo
     switch (DP) {
         case 20: hipLaunchKernelGGL(fourier16_presplit_kernel<20>, grid, dim3(64), 0, st, p); break;
         case 36: hipLaunchKernelGGL(fourier16_presplit_kernel<36>, grid, dim3(64), 0, st, p); break;
-        default: hipLaunchKernelGGL(fourier16_presplit_kernel<52>, grid, dim3(64), 0, st, p); break;
+        case 52: hipLaunchKernelGGL(fourier16_presplit_kernel<52>, grid, dim3(64), 0, st, p); break;
+        case 68: hipLaunchKernelGGL(fourier16_presplit_kernel<68>, grid, dim3(64), 0, st, p); break;
+        case 100: hipLaunchKernelGGL(fourier16_presplit_kernel<100>, grid, dim3(64), 0, st, p); break;
+        default: return GT_ENOTSUP;
     }
     GT_LAUNCH_CHECK();
     return 0;
@@ -667,7 +707,10 @@ extern "C" int gt_fourier16_attn(const void* F1, const void* F2, const void* T1,
     switch (DP) {
         case 20: fourier16_launch<20>(p, dual, block16 != 0, (int64_t)B * h, st); break;
         case 36: fourier16_launch<36>(p, dual, block16 != 0, (int64_t)B * h, st); break;
-        default: fourier16_launch<52>(p, dual, block16 != 0, (int64_t)B * h, st); break;
+        case 52: fourier16_launch<52>(p, dual, block16 != 0, (int64_t)B * h, st); break;
+        case 68: fourier16_launch<68>(p, dual, block16 != 0, (int64_t)B * h, st); break;
+        case 100: fourier16_launch<100>(p, dual, block16 != 0, (int64_t)B * h, st); break;
+        default: return GT_ENOTSUP;
     }
     GT_LAUNCH_CHECK();
     return 0;

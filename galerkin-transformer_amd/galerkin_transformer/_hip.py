@@ -1341,6 +1341,9 @@ def dft_synthesis(F, Z, Y, nb: int, n: int, P: int, Co: int, X2, W2, C2: int, bi
 
 
 FOURIER_DP = (20, 36, 52)
+# head-tile widths of the two-term fp16 Fourier kernels (gt_fourier16.hip): those of the fp32-MFMA kernel and the wide ones
+# (d_k = 64 / 96 with coordinates).  FOURIER_DP itself also keys gt_fourier_attn, gt_galerkin_dkv and gt_galerkin_dkv_ln.
+FOURIER16_DP = FOURIER_DP + (68, 100)
 
 
 def fourier16_active(precision: Optional[str] = None) -> bool:

@@ -1187,7 +1187,8 @@ class SimpleAttentionFn(Function):
             wpad = torch.zeros(d, h, DP, dtype=torch.float32, device=dev)
             wpad[:, :, :Dr] = wf.reshape(d, h, Dr)
             wpad = wpad.reshape(d, hD)
-            flash = (not need_w) and DP in H.FOURIER_DP
+            # (the wide head tiles, d_k = 64 / 96, have instances of the fp16 kernel only: in the f32 / bf16 modes they materialise)
+            flash = (not need_w) and (DP in H.FOURIER_DP or (DP in H.FOURIER16_DP and H.fourier16_active()))
             # fp16 arithmetic: the p = 0.5 score mask is drawn per 4 x 4 block (one hash per block: gt_hip.h), by the fused
             # kernels and by the materialising path alike; decided once per forward, the backward follows it
             blk16 = bool(H.fourier16_active() and d_attn is not None and H.fourier16_block_mask(d_attn))

@@ -457,7 +457,9 @@ int gt_fourier_attn(const float* F1, const float* F2, const float* T1, const flo
  *     gt_fourier16_image_bytes   size of ONE tensor's image block (header + images) for head tiles [B*n][h][DP]
  *     gt_fourier16_presplit      X0..X3 (up to four head-tile tensors, NULL-terminated) -> image blocks I0..I3, one launch
  *     gt_fourier16_attn          as gt_fourier_attn with F1, F2, T1, T2 = image blocks of the tensors named there
- * DP in {20, 36, 52}, else GT_ENOTSUP. */
+ * DP in {20, 36, 52, 68, 100} (d_k = 16 / 32 / 48 / 64 / 96 with one or two coordinate columns; 68 and 100 are additive, same
+ * ABI: older libraries answer them with 0 / GT_ENOTSUP), else GT_ENOTSUP and gt_fourier16_image_bytes returns 0.  A width
+ * that is a multiple of 32 has no instance (the image layout needs a partial last k-step). */
 int64_t gt_fourier16_image_bytes(int32_t B, int32_t n, int32_t h, int32_t DP);
 int gt_fourier16_presplit(const float* X0, const float* X1, const float* X2, const float* X3, void* I0, void* I1, void* I2,
                           void* I3, int32_t B, int32_t n, int32_t h, int32_t DP, void* stream);

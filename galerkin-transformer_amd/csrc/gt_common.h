@@ -9,6 +9,10 @@ namespace gt {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));     // one 32x32 MFMA accumulator of a lane
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));    // MFMA operand fragments
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int WAVE = 64;
 
@@ -57,6 +61,10 @@ __device__ inline uint32_t drop_key_dev(const DropDev& d) {
 __device__ inline float drop_mul(const DropDev& d, uint32_t key, uint32_t idx) {
     return (drop_hash(key, idx) >= d.thresh) ? d.scale : 0.f;
 }
+
+// 2^e from the exponent bits: exact for -126 <= e <= 127, and with e clamped to that (the normal) range
+__device__ __forceinline__ float pow2_f(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
+__device__ __forceinline__ float pow2_clamped(int e) { return pow2_f(e < -126 ? -126 : (e > 127 ? 127 : e)); }
 
 // Two fp32 values times a power of two s -> packed fp16 heads h0 = f16(x s) and residuals h1 = f16(x s - h0), in FOUR instructions:
 // v_fma_mix{lo,hi}_f16 evaluate the fp32 fma and round it (RNE, gradual underflow) into one half of the destination -- no

@@ -82,8 +82,7 @@ __device__ __forceinline__ void cw_split3(float a, float b, uint32_t (&out)[3]) 
 
 typedef _Float16 cw_f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 cw_f16x2 __attribute__((ext_vector_type(2)));
-constexpr int CWH_E0 = 120, CWH_TARGET = 13, CWH_LIMIT = 15;          // as X3H_* in gt_gemm_x3.hip
-__device__ __forceinline__ float cw_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
+constexpr int CWH_E0 = 120, CWH_TARGET = 13, CWH_LIMIT = 15;          // as X3H_* in gt_x3_core.h
 __device__ __forceinline__ void cw_split2h(float a, float b, uint32_t (&out)[3]) {      // two scaled values -> two packed fp16 pairs
     const f32x2 r = {a, b};
     const cw_f16x2 h0 = __builtin_convertvector(r, cw_f16x2);
@@ -223,7 +222,7 @@ __device__ __noinline__ void cw_loader(const float* base, int64_t ld, int H, int
             for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
             const int mx = (int)(__float_as_uint(m) >> 23);
             if (mx + e - 127 >= CWH_LIMIT) e = CWH_TARGET + 127 - mx;
-            scale = cw_pow2(e);
+            scale = pow2_f(e);
             if (lt == 0) exps[slot] = e;
         }
         st.store(buf + slot * (ROLE == 0 ? G::XSLOT : G::YBUF), scale);
@@ -332,7 +331,7 @@ __device__ __noinline__ void cw_mfma(float* slab, int Cin, int Cout, int ci0, in
             const int es = __builtin_amdgcn_readfirstlane(xexp[xslot] + gexp[y & 1]);
             if (es != eacc) {
                 const int dd = es - eacc;
-                const float f = dd < -126 ? 0.f : cw_pow2(dd);
+                const float f = dd < -126 ? 0.f : pow2_f(dd);
 #pragma unroll
                 for (int d = 0; d < 3; ++d)
 #pragma unroll
@@ -350,7 +349,7 @@ __device__ __noinline__ void cw_mfma(float* slab, int Cin, int Cout, int ci0, in
 
     // partial result: accumulator register r of lane (li, kq) = (x position 16 i + 4 kq + r, gy position 16 j + li)
     const int et = -eacc, etc = et < -126 ? -126 : (et > 126 ? 126 : et);
-    const float us = F16 ? cw_pow2(etc) : 1.f;
+    const float us = F16 ? pow2_f(etc) : 1.f;
     const int erest = F16 ? et - etc : 0;                  // non-zero only for operands ~2^-100 below unit scale
 #pragma unroll
     for (int d = 0; d < 3; ++d)

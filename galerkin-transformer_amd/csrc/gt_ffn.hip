@@ -33,16 +33,13 @@
 
 namespace gt {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void* ffn_lds_ptr;
 typedef const __attribute__((address_space(1))) void* ffn_glb_ptr;
 
 constexpr int FFN_BM = 64, FFN_BK = 16;
 constexpr int FFN_STAGE = FFN_BM * FFN_BK * 4;             // 4096 B: one A stage (64 rows x 16 k, fp32)
 constexpr int FFN_HSTRIDE = FFN_STAGE + 16;                // stage pitch of the H image (skewed: row reads across stages spread over the banks)
-constexpr int FFN_E0 = 120, FFN_TARGET = 13, FFN_LIMIT = 15;   // = X3H_* of gt_gemm_x3.hip
+constexpr int FFN_E0 = 120, FFN_TARGET = 13, FFN_LIMIT = 15;   // = X3H_* of gt_x3_core.h
 constexpr int FFN_EP_SW = 36;                              // staging row pitch (floats) of a wave's 64 x 32 out tile: 32 + 4
 
 __device__ __attribute__((aligned(16))) float ffn_zero[4] = {0.f, 0.f, 0.f, 0.f};
@@ -65,10 +62,9 @@ struct FfnP {
     float* out2; DropDev d2;
 };
 
-__device__ __forceinline__ float ffn_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
 __device__ __forceinline__ float ffn_alt(int parity) { return (parity & 1) ? -1.f : 1.f; }
 
-// this lane's 8 consecutive k (k-half lh) of tile row `row` from a stage image (gt_gemm_x3.hip: x3r_frag<0>)
+// this lane's 8 consecutive k (k-half lh) of tile row `row` from a stage image (gt_x3_core.h: x3r_frag<0>)
 __device__ __forceinline__ void ffn_frag(const char* __restrict__ img, int row, int lh, float (&v)[8]) {
     const int s = (row >> 2) & 3;
     const f32x4 a = *reinterpret_cast<const f32x4*>(img + row * 64 + (((2 * lh) ^ s) << 4));
@@ -91,14 +87,14 @@ __device__ __forceinline__ void ffn_tile_stage(const float (&v)[8], int& ea, flo
     if (__any(need)) {                                     // wave-uniform
         const int enew = need ? FFN_TARGET + 127 - ex : ea;
         const int dlt = enew - ea;                         // <= 0
-        const float f = dlt < -126 ? 0.f : ffn_pow2(dlt);
+        const float f = dlt < -126 ? 0.f : pow2_f(dlt);
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[j][e] *= f;
         ea = enew;
     }
-    const float sv = ffn_pow2(ea) * sgn;
+    const float sv = pow2_f(ea) * sgn;
     uint32_t q[4][2];
 #pragma unroll
     for (int t = 0; t < 4; ++t) f16_mulsplit_pair(v[2 * t], sv, v[2 * t + 1], sv, q[t][0], q[t][1]);
@@ -119,7 +115,7 @@ __device__ __forceinline__ void ffn_tile_stage(const float (&v)[8], int& ea, flo
 // un-scale one accumulator (row exponent of the lane, tile exponent of the packed columns) with the alternating sign
 __device__ __forceinline__ void ffn_unscale(f32x16& a, int ea, int eb, float sgn) {
     const int et = -(ea + eb), etc = et < -126 ? -126 : (et > 126 ? 126 : et);
-    const float sg = ffn_pow2(etc) * sgn;
+    const float sg = pow2_f(etc) * sgn;
 #pragma unroll
     for (int e = 0; e < 16; ++e) a[e] *= (e & 1) ? -sg : sg;
     if (et != etc) {
@@ -285,7 +281,7 @@ __global__ __launch_bounds__(256, 2) void ffn_fwd16_kernel(const FfnP p) {
             const float a = fmaxf(fmaxf(tab[row], tab[64 + row]), fmaxf(tab[128 + row], tab[192 + row]));
             const int ex = (int)(__float_as_uint(a) >> 23);
             er[i] = ex == 0 ? 0 : min(FFN_E0, FFN_TARGET + 127 - ex);      // scaled row amax in [2^13, 2^14)
-            const float sv = ffn_pow2(er[i]) * ffn_alt(i);
+            const float sv = pow2_f(er[i]) * ffn_alt(i);
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll

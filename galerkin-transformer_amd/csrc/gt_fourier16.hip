@@ -51,10 +51,6 @@ struct F16G {
     static_assert(DP % 4 == 0 && TC > 0 && RM_BYTES % 1024 == 0 && TR_BYTES % 1024 == 0, "image chunks are 1 KiB");
 };
 
-__device__ __forceinline__ float f16_pow2(int e) {                        // 2^e, e clamped to the normal range
-    e = e < -126 ? -126 : (e > 127 ? 127 : e);
-    return __uint_as_float((uint32_t)(e + 127) << 23);
-}
 __device__ __forceinline__ float f16_wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -108,7 +104,7 @@ __global__ __launch_bounds__(64) void fourier16_presplit_kernel(const F16PreP p)
     const int be = (int)(__float_as_uint(amax) >> 23);
     int ex = be == 0 ? 0 : 140 - be;                   // amax 2^ex in [2^13, 2^14)
     ex = ex > 126 ? 126 : ex;
-    const float sc = f16_pow2(ex);
+    const float sc = pow2_clamped(ex);
     float nr = 0.f;
     if (lane < 32)
         for (int c = 0; c < DP; ++c) {
@@ -348,7 +344,7 @@ __global__ __launch_bounds__(64 * NW, (f16_waves_per_simd<DP, DUAL, NW>())) void
                 }
                 EA = cap;
             }
-            sigA = osign * f16_pow2(EA - e1 - ef1 - e2);
+            sigA = osign * pow2_clamped(EA - e1 - ef1 - e2);
         }
         if (DUAL) {
             const int cap = 15 - l2 - lf2 + e2 + ef2 + e1;
@@ -364,7 +360,7 @@ __global__ __launch_bounds__(64 * NW, (f16_waves_per_simd<DP, DUAL, NW>())) void
                 }
                 EB = cap;
             }
-            sigB = osign * f16_pow2(EB - e2 - ef2 - e1);
+            sigB = osign * pow2_clamped(EB - e2 - ef2 - e1);
         }
         // keep masks of this tile's score elements (dropout modes), in front of the first product in program order: they do
         // not depend on it, and the sched_group_barrier sequence behind the product interleaves them with its MFMAs

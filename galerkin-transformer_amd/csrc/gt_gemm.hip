@@ -495,7 +495,7 @@ static bool has_epilogue(const gt_gemm_desc* d) {
            d->out_scale != 1.f || d->ep_mode != GT_EP_NORMAL || d->K2 > 0;
 }
 
-// number of bf16 planes the split-operand kernel (gt_gemm_x3.hip) would use for d, 0 = fp32 MFMA kernels
+// number of bf16 planes the split-operand kernels (gt_x3_core.h) would use for d, 0 = fp32 MFMA kernels
 static int x3_planes(const gt_gemm_desc* d) {
     // GT_PREC_F16X2: the packed-B kernels run the two-term fp16 arithmetic, every other split-operand launch bf16x3
     const int planes = (d->precision == GT_PREC_BF16X3 || d->precision == GT_PREC_F16X2) ? 3

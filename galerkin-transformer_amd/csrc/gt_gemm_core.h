@@ -411,7 +411,10 @@ __device__ __forceinline__ void head_epilogue(const GemmP& p, const f32x4 (&acc)
 }
 
 
-// split-operand bf16 kernel (gt_gemm_x3.hip)
+// split-operand kernels: host dispatch in gt_gemm_x3.hip, kernel families in gt_gemm_x3.hip / gt_gemm_x3p.hip / gt_gemm_x3w.hip
+// The instance x3_launch starts and x3_kernel_name prints: the family and the template arguments it takes from these.
+enum X3Family { X3_STAGED, X3_RING, X3_PACKED, X3_PACKED_H, X3_WGRAD };    // gemm_x3_ / x3r_ / x3p_ / x3h_ / x3w_kernel
+struct X3Pick { X3Family family; int LA, LB, PLANES, HN, CV, BN; };
 bool x3_shape_ok(const gt_gemm_desc* d);
 bool x3_headnorm_ok(const GemmP& p, int layout_a, int layout_b, int planes);
 int x3_launch(const GemmP& p, int layout_a, int layout_b, int planes, unsigned tiles, unsigned split, unsigned batch,
@@ -425,5 +428,8 @@ int x3_pack_b_many(const gt_gemm_desc* descs, void* const* outs, int n, hipStrea
 int x3_pack_b(const gt_gemm_desc* d, GemmP& p, void* ws, int64_t ws_bytes, hipStream_t st);
 inline int hn_slot_width(int dk) { return dk == 48 ? 64 : dk; }     // head width -> columns of its slot in the N dimension
 bool x3w_ok(const gt_gemm_desc* d, int split);
+// launchers of the families that live in their own translation units (called by x3_launch)
+int x3h_launch(const GemmP& p, const X3Pick& k, dim3 grid, hipStream_t st);
+int x3w_launch(const GemmP& p, unsigned tiles, unsigned split, hipStream_t st);
 
 }  // namespace gt

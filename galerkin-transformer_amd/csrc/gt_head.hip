@@ -327,10 +327,6 @@ typedef _Float16 hf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 hf16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t hu32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float h16_pow2(int e) {                       // 2^e, e clamped to the normal range
-    e = e < -126 ? -126 : (e > 127 ? 127 : e);
-    return __uint_as_float((uint32_t)(e + 127) << 23);
-}
 // exponent that puts amax (>= 0) into [2^14, 2^15); 0 for amax = 0 / subnormal
 __device__ __forceinline__ int h16_exp_for(float amax) {
     const int ex = (int)(__float_as_uint(amax) >> 23);
@@ -387,7 +383,7 @@ __device__ __forceinline__ int head16_stage(const HeadP& p, hu32x4* sW1, hu32x4*
     }
     __syncthreads();
     const int eW = h16_exp_for(fmaxf(fmaxf(sRed[0], sRed[1]), fmaxf(sRed[2], sRed[3])));
-    const float sw = h16_pow2(eW);
+    const float sw = pow2_clamped(eW);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         hf16x8 hi, lo;
@@ -420,7 +416,7 @@ __device__ __forceinline__ int head16_split_row(const float (&xs)[8], hf16x8& xh
     m = fmaxf(m, __shfl_xor(m, 16, 64));
     m = fmaxf(m, __shfl_xor(m, 32, 64));
     const int ex = h16_exp_for(m);
-    h16_split8(xs, h16_pow2(ex), xh, xl);
+    h16_split8(xs, pow2_clamped(ex), xh, xl);
     return ex;
 }
 
@@ -451,7 +447,7 @@ __global__ __launch_bounds__(256, 2) void head_fwd16_kernel(const HeadP p) {
         }
         hf16x8 xh, xl;
         const int ex = head16_split_row(xs, xh, xl);
-        const float us = h16_pow2(-ex) * h16_pow2(-eW);
+        const float us = pow2_clamped(-ex) * pow2_clamped(-eW);
         float part = 0.f;
 #pragma unroll
         for (int mt = 0; mt < 8; ++mt) {
@@ -494,7 +490,7 @@ __global__ __launch_bounds__(256, 2) void head_bwd16_kernel(const HeadP p) {
     const int j = lane & 15, kq = lane >> 4;
     const int pair = wave >> 1, half = wave & 1, hb = 64 * half;
     const int eW = head16_stage<true>(p, sW1, sWT, sB1, sW2, sRed);
-    const float usW = h16_pow2(-eW);
+    const float usW = pow2_clamped(-eW);
     float* dh = sDh + wave * 32 * DH16P;
     float* fr = sF + wave * 32;
 
@@ -543,8 +539,8 @@ __global__ __launch_bounds__(256, 2) void head_bwd16_kernel(const HeadP p) {
             m = fmaxf(m, __shfl_xor(m, 16, 64));
             m = fmaxf(m, __shfl_xor(m, 32, 64));
             const int ex = h16_exp_for(m);
-            h16_split8(xs, h16_pow2(ex), xh[u], xl[u]);
-            us[u] = h16_pow2(-ex) * usW;
+            h16_split8(xs, pow2_clamped(ex), xh[u], xl[u]);
+            us[u] = pow2_clamped(-ex) * usW;
             xm[u] = m;
             g[u] = active ? gv[u] : 0.f;
         }
@@ -582,12 +578,12 @@ __global__ __launch_bounds__(256, 2) void head_bwd16_kernel(const HeadP p) {
                 dm = fmaxf(dm, __shfl_xor(dm, 16, 64));
                 dm = fmaxf(dm, __shfl_xor(dm, 32, 64));
                 const int ed = h16_exp_for(dm);
-                const float sd = h16_pow2(ed);
+                const float sd = pow2_clamped(ed);
                 // a row without gradient (padding, or every unit switched off) takes no part in (3): factor 0, and it
                 // must not set the wave's exponent
                 const bool live = (__float_as_uint(dm) >> 23) != 0;
                 edh[u] = live ? ed : 100000;
-                rowmag[u] = live ? xm[u] * h16_pow2(-ed) : 0.f;
+                rowmag[u] = live ? xm[u] * pow2_clamped(-ed) : 0.f;
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt) {
 #pragma unroll
@@ -610,7 +606,7 @@ __global__ __launch_bounds__(256, 2) void head_bwd16_kernel(const HeadP p) {
                         accX[ti] = h16_mma3(wh, wl, dhi, dlo, accX[ti]);
                     }
                 }
-                const float ux = h16_pow2(-ed) * usW;
+                const float ux = pow2_clamped(-ed) * usW;
                 accX[0] *= ux;
                 accX[1] *= ux;
             }
@@ -646,7 +642,7 @@ __global__ __launch_bounds__(256, 2) void head_bwd16_kernel(const HeadP p) {
             const int xe = (int)(__float_as_uint(mag) >> 23);
             if (xe != 0 && xe + cexp - 127 >= H16_LIMIT) {             // wave-uniform
                 const int cn = H16_TARGET + 127 - xe, dlt = cn - cexp;
-                const float f = dlt < -126 ? 0.f : h16_pow2(dlt);
+                const float f = dlt < -126 ? 0.f : pow2_clamped(dlt);
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt) {
                     accW[mt][0] *= f;
@@ -659,7 +655,7 @@ __global__ __launch_bounds__(256, 2) void head_bwd16_kernel(const HeadP p) {
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
                     const int fe = cexp - edh[u];
-                    fr[16 * u + j] = fe < -126 ? 0.f : h16_pow2(fe);
+                    fr[16 * u + j] = fe < -126 ? 0.f : pow2_clamped(fe);
                 }
             }
             const f32x4 f0 = *reinterpret_cast<const f32x4*>(&fr[8 * kq]);
@@ -688,7 +684,7 @@ __global__ __launch_bounds__(256, 2) void head_bwd16_kernel(const HeadP p) {
     }
     // un-scale the weight-gradient accumulators
     {
-        const float uc = h16_pow2(-cexp);
+        const float uc = pow2_clamped(-cexp);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
             accW[mt][0] *= uc;

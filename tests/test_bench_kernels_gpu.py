@@ -181,7 +181,7 @@ def test_whole_model_darcy141_vs_oracle(gpu_device, mode, scaler_act):
     float32 oracle deviates from the float64 one by up to 1e-5 on the encoder parameters at B = 9).  Until round 4 the
     default split-operand arithmetic sat ~10x above that (1.6e-4 at B = 9): the bf16 MFMA chops addends toward -infinity,
     a coherent offset that every reduction over tokens preserves (tools/parity_bisect.py, tools/mfma_chain_probe.hip,
-    DESIGN.md section 2); with the sign-alternating accumulation of gt_gemm_x3.hip it measures 1.2e-5 (float32 oracle
+    DESIGN.md section 2); with the sign-alternating accumulation of gt_x3_core.h it measures 1.2e-5 (float32 oracle
     9.2e-6, fp32-MFMA kernels 1.4e-5) and takes the same gate as everything else."""
     sys.path.insert(0, ROOT)
     import bench

@@ -382,7 +382,7 @@ def _mfma32(first, second, acc):
 
 @pytest.mark.parametrize("conv", [False, True])
 def test_packed_b_kernel_lane_map(conv):
-    """gemm_x3p_kernel (gt_gemm_x3.hip), one 128 x 128 block tile: x3_pack_b_kernel's fragment order, the wave's B
+    """gemm_x3p_kernel (gt_gemm_x3.hip), one 128 x 128 block tile: x3_pack_b_kernel's (gt_gemm_x3p.hip) fragment order, the wave's B
     fragment addresses, the A rows of a stage (plain, or the implicit 3x3 convolution: channel block -> tap -> channel
     stage order, tap-valid bits, neighbour-row offsets) and the accumulator -> (row, column) map of the epilogue,
     against A B^T / conv2d restated in numpy.  Values stay float64: the bf16 split is exact and tested on the GPU."""
@@ -507,7 +507,7 @@ def test_wave_sum_lane63_dpp_model():
 
 @pytest.mark.parametrize("W4", [9, 10, 13, 17, 18, 20, 21])
 def test_headnorm_tile_store_walk(W4):
-    """x3_epilogue_hn (gt_gemm_x3.hip): the staged 32 x W4 tile of 16-byte granules is stored 64 granules per instruction;
+    """x3_epilogue_hn (gt_x3_core.h): the staged 32 x W4 tile of 16-byte granules is stored 64 granules per instruction;
     lane l owns granules e = l + 64 it and walks (row, column) incrementally -- the walk equals divmod(e, W4), covers every
     granule of the 32 rows exactly once in nit = ceil(32 W4 / 64) iterations (+ the chunk-of-three overrun, all past row 31)."""
     nit = (32 * W4 + 63) >> 6
@@ -529,7 +529,7 @@ def test_headnorm_tile_store_walk(W4):
 
 @pytest.mark.parametrize("MI", [1, 2])
 def test_fast_epilogue_batches_cover_wave_tile(MI):
-    """x3_epilogue_fast (gt_gemm_x3.hip): a wave's (32 MI) x 64 tile leaves in 2 MI batches of four 256-byte row segments
+    """x3_epilogue_fast (gt_x3_core.h): a wave's (32 MI) x 64 tile leaves in 2 MI batches of four 256-byte row segments
     per lane group; batch b reads staging rows 16 (b & 1) + 4 k + rsub of row tile b >> 1 and writes output row
     mtile0 + 16 b + 4 k + rsub, columns 4 c4 .. + 3 -- every element exactly once, from the accumulator the MFMA left it in."""
     acc = np.arange(MI * 2 * 64 * 16, dtype=np.int64).reshape(MI, 2, 64, 16)     # [i][j][lane][register]
@@ -746,7 +746,7 @@ def test_head_backward16_lane_map(T):
 
 @pytest.mark.parametrize("tiles,n_split", [(1, 256), (2, 256), (2, 171), (3, 171), (3, 8), (2, 5)])
 def test_x3w_chunk_major_block_order(tiles, n_split):
-    """gemm_x3w_kernel with x3w_map (gt_gemm_x3.hip): a 1-D grid of 8 ceil(n_split / 8) tiles blocks, block id % 8 = XCD;
+    """gemm_x3w_kernel with x3w_map (gt_gemm_x3w.hip): a 1-D grid of 8 ceil(n_split / 8) tiles blocks, block id % 8 = XCD;
     XCD x owns the K chunks [x spx, (x + 1) spx) and the tiles of one chunk are consecutive blocks of that XCD.  Every
     (tile, chunk) pair is worked exactly once, surplus blocks leave, and a chunk's tiles share an XCD back to back."""
     spx = (n_split + 7) >> 3
@@ -797,7 +797,7 @@ def test_conv0_decision_bits_layout(Cout, npx):
 
 @pytest.mark.parametrize("K,with_acs", [(64, True), (45, False)])
 def test_x3w_kernel_lane_map(K, with_acs):
-    """gemm_x3w_kernel (gt_gemm_x3.hip), one 128 x 128 output tile of one K chunk: the staging roles (waves 0-1 the A tile,
+    """gemm_x3w_kernel (gt_gemm_x3w.hip), one 128 x 128 output tile of one K chunk: the staging roles (waves 0-1 the A tile,
     2-3 the B tile; a thread owns rows 4 r4 .. + 3 and the eight tokens of k-group kg), the plane layout [k-group][row] of
     16-byte units (eight tokens of one row), the fragment a lane reads for MFMA k-step ks (unit 2 ks + lh of its row), the
     operand order of the MFMA (N-side tile first), the sign alternation of odd rows on both sides and its undo, the slab

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <atomic>
 #include "gt_hip.h"
 
@@ -145,7 +146,30 @@ __device__ __forceinline__ float wave_sum_lane63(float v) {
     return v;
 }
 
+// Four values of a head-tile row [pos(p) | values | pad]: the p columns in front decide the widest aligned access.
+__device__ __forceinline__ void tile_store4(float* __restrict__ dst, int p, f32x4 v) {
+    if ((p & 3) == 0) *reinterpret_cast<f32x4*>(dst) = v;
+    else if ((p & 1) == 0) {
+        *reinterpret_cast<f32x2*>(dst) = f32x2{v[0], v[1]};
+        *reinterpret_cast<f32x2*>(dst + 2) = f32x2{v[2], v[3]};
+    } else { dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3]; }
+}
+__device__ __forceinline__ f32x4 tile_load4(const float* __restrict__ src, int p) {
+    if ((p & 3) == 0) return *reinterpret_cast<const f32x4*>(src);
+    if ((p & 1) == 0) {
+        const f32x2 a = *reinterpret_cast<const f32x2*>(src), b = *reinterpret_cast<const f32x2*>(src + 2);
+        return f32x4{a[0], a[1], b[0], b[1]};
+    }
+    return f32x4{src[0], src[1], src[2], src[3]};
+}
+
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+inline int round4(int v) { return (v + 3) & ~3; }
+
+// Launcher-side check of a pointer list: true if any of them is off an N-byte boundary.  A null pointer counts as aligned.
+template <unsigned N, typename... P>
+inline bool misaligned(const P*... ptrs) { return ((reinterpret_cast<uintptr_t>(ptrs) | ...) & (N - 1)) != 0; }
+template <typename... P> inline bool misaligned16(const P*... ptrs) { return misaligned<16>(ptrs...); }
 
 // tall-skinny weight-gradient path of gt_gemm (gt_tsmm.hip)
 bool tsmm_eligible(const gt_gemm_desc* d);
@@ -174,6 +198,13 @@ int gt_allow_dynamic_lds(size_t bytes) {
         return GT_ENOTSUP;
     done.fetch_or(bit, std::memory_order_release);
     return 0;
+}
+// kernels whose dynamic LDS may exceed 64 KiB opt in to the whole 160 KiB (host-side attribute, not a stream op)
+template <auto K>
+int allow_big_lds(size_t bytes) {
+    if (bytes <= 64 * 1024) return 0;
+    if (bytes > 160 * 1024) return GT_ENOTSUP;
+    return gt_allow_dynamic_lds<K>(160 * 1024);
 }
 
 }  // namespace gt

@@ -487,7 +487,6 @@ static void launch_stream(hipStream_t st, const GemmP& p) {
 
 struct Plan { int cfg, bm, bn, bk, tiles_m, tiles_n, split, k_chunk, stream, x3; };
 
-static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline bool m4(int64_t v) { return (v & 3) == 0; }
 
 static bool has_epilogue(const gt_gemm_desc* d) {
@@ -546,7 +545,7 @@ static int make_plan(const gt_gemm_desc* d, Plan* pl) {
     // streamed kernel: 128-wide N tiles, 16-byte aligned operands, whole granules at every edge
     // (measured: it wins from K = 256 up; at K = 128 a tile is only 4 stages long and the v1 kernel's
     // higher occupancy hides the per-tile epilogue better)
-    pl->stream = (c <= 1) && d->K >= 256 && (d->K & 3) == 0 && al16(d->A) && al16(d->B) && m4(d->lda) &&
+    pl->stream = (c <= 1) && d->K >= 256 && (d->K & 3) == 0 && !misaligned16(d->A, d->B) && m4(d->lda) &&
                  m4(d->ldb) && m4(d->a_bs0) && m4(d->a_bs1) && m4(d->b_bs0) && m4(d->b_bs1) &&
                  (d->layout_a == 0 || (d->M & 3) == 0) && (d->layout_b == 0 || (d->N & 3) == 0);
     if (const char* e = getenv("GT_GEMM_STREAM")) pl->stream = pl->stream && atoi(e) != 0;
@@ -653,8 +652,8 @@ extern "C" int gt_gemm_kernel_name(const gt_gemm_desc* d, char* buf, int32_t n) 
         q.M = d->M; q.N = d->N; q.K = d->K; q.K2 = d->K2; q.cv_C = d->cv_c; q.cv_wgrad = d->cv_wgrad != 0;
         if (x3_packed_ok(d, pl.x3, pl.split)) { q.Bp = d->B; q.bp_f16 = d->precision == GT_PREC_F16X2; }
         q.wg_f16 = x3w_ok(d, pl.split);
-        q.a_vec = al16(d->A) && m4(d->lda) && m4(d->a_bs0) && m4(d->a_bs1);
-        q.b_vec = al16(d->B) && m4(d->ldb) && m4(d->b_bs0) && m4(d->b_bs1);
+        q.a_vec = !misaligned16(d->A) && m4(d->lda) && m4(d->a_bs0) && m4(d->a_bs1);
+        q.b_vec = !misaligned16(d->B) && m4(d->ldb) && m4(d->b_bs0) && m4(d->b_bs1);
         snprintf(buf, n, "%s", x3_kernel_name(q, d->layout_a, d->layout_b, pl.x3,
                                               d->ep_mode == GT_EP_HEADNORM ? hn_slot_width(d->hn_dk) : 0));
     }
@@ -745,8 +744,8 @@ static int gemm_one(const gt_gemm_desc* d, int drop_ld, int n_off, void* ws, int
     p.n_work = (int)n_work64;
     p.A = d->A; p.lda = d->lda; p.a_bs0 = d->a_bs0; p.a_bs1 = d->a_bs1;
     p.B = d->B; p.ldb = d->ldb; p.b_bs0 = d->b_bs0; p.b_bs1 = d->b_bs1;
-    p.a_vec = al16(d->A) && m4(d->lda) && m4(d->a_bs0) && m4(d->a_bs1);
-    p.b_vec = al16(d->B) && m4(d->ldb) && m4(d->b_bs0) && m4(d->b_bs1);
+    p.a_vec = !misaligned16(d->A) && m4(d->lda) && m4(d->a_bs0) && m4(d->a_bs1);
+    p.b_vec = !misaligned16(d->B) && m4(d->ldb) && m4(d->b_bs0) && m4(d->b_bs1);
     p.a_drop = make_drop(&d->a_drop, d->a_drop_sign);
     p.a_drop_ld = d->a_drop_ld; p.a_drop_bstride = d->a_drop_bstride;
     if (d->cv_c > 0) {
@@ -756,10 +755,10 @@ static int gemm_one(const gt_gemm_desc* d, int drop_ld, int n_off, void* ws, int
         // read a channel slice of a wider channels-last buffer in place (values below cv_c mean "dense")
         if (d->cv_wgrad) {
             p.ldb = d->ldb > d->cv_c ? d->ldb : d->cv_c; p.b_bs0 = p.b_bs1 = 0;
-            p.b_vec = al16(d->B) && m4(p.ldb);
+            p.b_vec = !misaligned16(d->B) && m4(p.ldb);
         } else {
             p.lda = d->lda > d->cv_c ? d->lda : d->cv_c;
-            p.a_vec = al16(d->A) && m4(p.lda);
+            p.a_vec = !misaligned16(d->A) && m4(p.lda);
         }
     }
 
@@ -767,8 +766,8 @@ static int gemm_one(const gt_gemm_desc* d, int drop_ld, int n_off, void* ws, int
         if (!d->A2 || !d->B2 || d->a_drop.p > 0.f || d->a_colsum || pl.split != 1) return GT_ENOTSUP;
         p.K2 = d->K2; p.A2 = d->A2; p.lda2 = d->lda2; p.a2_bs0 = d->a2_bs0; p.a2_bs1 = d->a2_bs1;
         p.B2 = d->B2; p.ldb2 = d->ldb2; p.b2_bs0 = d->b2_bs0; p.b2_bs1 = d->b2_bs1;
-        p.a2_vec = al16(d->A2) && m4(d->lda2) && m4(d->a2_bs0) && m4(d->a2_bs1);
-        p.b2_vec = al16(d->B2) && m4(d->ldb2) && m4(d->b2_bs0) && m4(d->b2_bs1);
+        p.a2_vec = !misaligned16(d->A2) && m4(d->lda2) && m4(d->a2_bs0) && m4(d->a2_bs1);
+        p.b2_vec = !misaligned16(d->B2) && m4(d->ldb2) && m4(d->b2_bs0) && m4(d->b2_bs1);
     }
     const int64_t mn = (int64_t)d->M * d->N;
     float* dw2_partial = nullptr;
@@ -811,16 +810,16 @@ static int gemm_one(const gt_gemm_desc* d, int drop_ld, int n_off, void* ws, int
         if (!ws || ws_bytes < need) return GT_EWS;
         p.C = reinterpret_cast<float*>(ws);
         p.ldc = d->N; p.c_bs0 = (int64_t)d->batch1 * mn; p.c_bs1 = mn; p.c_split = batch * mn;
-        p.c_vec = al16(ws) && m4(d->N) && m4(mn);
+        p.c_vec = !misaligned16(ws) && m4(d->N) && m4(mn);
         p.raw = 1;
         p.alpha = 1.f; p.out_scale = 1.f;
     } else {
         p.C = d->C; p.ldc = d->ldc; p.c_bs0 = d->c_bs0; p.c_bs1 = d->c_bs1; p.c_split = 0;
-        p.c_vec = al16(d->C) && m4(d->ldc) && m4(d->c_bs0) && m4(d->c_bs1);
-        if (d->res) p.c_vec = p.c_vec && al16(d->res) && m4(d->ldr) && m4(d->r_bs0) && m4(d->r_bs1);
-        if (d->add) p.c_vec = p.c_vec && al16(d->add) && m4(d->ldadd) && m4(d->add_bs0) && m4(d->add_bs1);
-        if (d->aux_op) p.c_vec = p.c_vec && al16(d->aux) && m4(d->ldaux) && m4(d->aux_bs0) && m4(d->aux_bs1);
-        if (d->pre) p.c_vec = p.c_vec && al16(d->pre) && m4(d->ldpre) && m4((int64_t)d->M * d->ldpre);
+        p.c_vec = !misaligned16(d->C) && m4(d->ldc) && m4(d->c_bs0) && m4(d->c_bs1);
+        if (d->res) p.c_vec = p.c_vec && !misaligned16(d->res) && m4(d->ldr) && m4(d->r_bs0) && m4(d->r_bs1);
+        if (d->add) p.c_vec = p.c_vec && !misaligned16(d->add) && m4(d->ldadd) && m4(d->add_bs0) && m4(d->add_bs1);
+        if (d->aux_op) p.c_vec = p.c_vec && !misaligned16(d->aux) && m4(d->ldaux) && m4(d->aux_bs0) && m4(d->aux_bs1);
+        if (d->pre) p.c_vec = p.c_vec && !misaligned16(d->pre) && m4(d->ldpre) && m4((int64_t)d->M * d->ldpre);
         p.alpha = d->alpha; p.bias = d->bias;
         p.rp = d->rp; p.rp_a = d->rp_a; p.rp_lda = d->rp_lda; p.rp_a_bs0 = d->rp_a_bs0;
         p.rp_b = d->rp_b; p.rp_ldb = d->rp_ldb;
@@ -838,7 +837,7 @@ static int gemm_one(const gt_gemm_desc* d, int drop_ld, int n_off, void* ws, int
             if (batch != 1 || d->ep_mode != GT_EP_NORMAL || d->K2 > 0) return GT_ENOTSUP;
             if (d->c_mask.p < 0.f || d->c_mask.p >= 1.f || (d->c_mask.p > 0.f && !d->c_mask.seed)) return GT_EINVAL;
             p.c2 = d->c_masked; p.ldc2 = d->ldc_masked; p.drop2 = make_drop(&d->c_mask);
-            p.c_vec = p.c_vec && al16(d->c_masked) && m4(d->ldc_masked);
+            p.c_vec = p.c_vec && !misaligned16(d->c_masked) && m4(d->ldc_masked);
         }
     }
     if (d->c_masked && pl.split > 1) return GT_ENOTSUP;
@@ -895,7 +894,7 @@ static int gemm_one(const gt_gemm_desc* d, int drop_ld, int n_off, void* ws, int
 
     if (pl.split > 1) {
         const int64_t total = batch * mn;
-        const bool v4 = m4(d->N) && m4(d->ldc) && m4(d->c_bs0) && m4(d->c_bs1) && al16(d->C) && al16(ws);
+        const bool v4 = m4(d->N) && m4(d->ldc) && m4(d->c_bs0) && m4(d->c_bs1) && !misaligned16(d->C, ws);
         if (v4) {
             const int64_t total4 = total / 4;
             const int blocks4 = (int)((total4 + 31) / 32);

@@ -1,0 +1,382 @@
+// Per-head LayerNorm of the Q / K / V projections with the position concat (gfx950): [T][3 h dk] -> head tiles
+// [3][T][h][DP] = [pos(p) | values(dk) | pad], forward and backward, in two generations: the LDS-staged kernels take any
+// shape, the bandwidth-shaped v2 kernels take dk % 4 == 0 with 16-byte aligned operands (head_geom decides).  The backward
+// leaves d(gamma), d(beta) partials per block; gt_slab_reduce sums them in a fixed order.
+#include "gt_common.h"
+
+namespace gt {
+
+// One block handles HN_TOK tokens.  LDS image: seg[tok][3h][dk+1] (pad 1 -> a thread walking its own
+// segment is conflict-free against its neighbours).
+constexpr int HN_TOK_MAX = 16;
+// tokens per block such that the LDS image stays <= ~48 KiB
+static inline int hn_tok(int per_token_floats) {
+    int t = 12000 / std::max(per_token_floats, 1);
+    return std::max(1, std::min(t, HN_TOK_MAX));
+}
+
+__global__ __launch_bounds__(256) void headnorm_fwd_kernel(
+    const float* __restrict__ qkv, const float* __restrict__ pos, const float* __restrict__ gamma,
+    const float* __restrict__ beta, int T, int h, int dk, int p, int DP, int norm_mask, float eps,
+    float* __restrict__ out, float* __restrict__ stats, int HN_TOK) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int d3 = 3 * h * dk, S = 3 * h, pitch = dk + 1;
+    const int t0 = blockIdx.x * HN_TOK, nt = min(HN_TOK, T - t0);
+    for (int e = threadIdx.x; e < nt * d3; e += blockDim.x) {
+        const int tok = e / d3, f = e % d3;
+        lds[(tok * S + f / dk) * pitch + (f % dk)] = qkv[(int64_t)(t0 + tok) * d3 + f];
+    }
+    __syncthreads();
+    for (int it = threadIdx.x; it < nt * S; it += blockDim.x) {
+        const int tok = it / S, s = it % S, stream = s / h, head = s % h;
+        if (!((norm_mask >> stream) & 1)) continue;
+        int ni = 0;
+        for (int q = 0; q < stream; ++q) ni += (norm_mask >> q) & 1;
+        float* v = lds + it * pitch;
+        float mu = 0.f;
+        for (int j = 0; j < dk; ++j) mu += v[j];
+        mu /= dk;
+        float var = 0.f;
+        for (int j = 0; j < dk; ++j) { const float c = v[j] - mu; var += c * c; }
+        var /= dk;
+        const float rstd = 1.f / sqrtf(var + eps);
+        const float* g = gamma + (ni * h + head) * dk;
+        const float* b = beta + (ni * h + head) * dk;
+        for (int j = 0; j < dk; ++j) v[j] = (v[j] - mu) * rstd * g[j] + b[j];
+        float* st = stats + (((int64_t)ni * T + t0 + tok) * h + head) * 2;
+        st[0] = mu;
+        st[1] = rstd;
+    }
+    __syncthreads();
+    const int per_stream = nt * h * DP;
+    for (int e = threadIdx.x; e < 3 * per_stream; e += blockDim.x) {
+        const int stream = e / per_stream, r = e % per_stream;
+        const int tok = r / (h * DP), head = (r / DP) % h, c = r % DP;
+        float val = 0.f;
+        if (c < p) val = pos[(int64_t)(t0 + tok) * p + c];
+        else if (c < p + dk) val = lds[(tok * S + stream * h + head) * pitch + (c - p)];
+        out[((int64_t)stream * T + t0) * h * DP + r] = val;
+    }
+}
+
+__global__ __launch_bounds__(256) void headnorm_bwd_kernel(
+    const float* __restrict__ d_out, const float* __restrict__ qkv, const float* __restrict__ gamma,
+    const float* __restrict__ stats, int T, int h, int dk, int p, int DP, int norm_mask,
+    float* __restrict__ d_qkv, float* __restrict__ partial /* [nblk][2(dg,db)][2][h][dk] */, int HN_TOK) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int d3 = 3 * h * dk, S = 3 * h, pitch = dk + 1;
+    float* xs = lds;                              // raw -> xhat   [HN_TOK][S][pitch]
+    float* dy = lds + HN_TOK * S * pitch;         // upstream grad [HN_TOK][S][pitch]
+    float* m1 = dy + HN_TOK * S * pitch;          // [HN_TOK*S]
+    float* m2 = m1 + HN_TOK * S;
+    float* rs = m2 + HN_TOK * S;
+    const int ngroups = (T + HN_TOK - 1) / HN_TOK;
+    for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const bool first = (grp == (int)blockIdx.x);
+    const int t0 = grp * HN_TOK, nt = min(HN_TOK, T - t0);
+    __syncthreads();
+    for (int e = threadIdx.x; e < nt * d3; e += blockDim.x) {
+        const int tok = e / d3, f = e % d3, s = f / dk, j = f % dk;
+        xs[(tok * S + s) * pitch + j] = qkv[(int64_t)(t0 + tok) * d3 + f];
+        const int stream = s / h, head = s % h;
+        dy[(tok * S + s) * pitch + j] =
+            d_out[(((int64_t)stream * T + t0 + tok) * h + head) * DP + p + j];
+    }
+    __syncthreads();
+    for (int it = threadIdx.x; it < nt * S; it += blockDim.x) {
+        const int tok = it / S, s = it % S, stream = s / h, head = s % h;
+        if (!((norm_mask >> stream) & 1)) continue;
+        int ni = 0;
+        for (int q = 0; q < stream; ++q) ni += (norm_mask >> q) & 1;
+        const float* st = stats + (((int64_t)ni * T + t0 + tok) * h + head) * 2;
+        const float mu = st[0], rstd = st[1];
+        const float* g = gamma + (ni * h + head) * dk;
+        float* x = xs + it * pitch;
+        const float* gy = dy + it * pitch;
+        float a1 = 0.f, a2 = 0.f;
+        for (int j = 0; j < dk; ++j) {
+            const float xh = (x[j] - mu) * rstd;
+            x[j] = xh;
+            const float gg = gy[j] * g[j];
+            a1 += gg;
+            a2 += gg * xh;
+        }
+        m1[it] = a1 / dk;
+        m2[it] = a2 / dk;
+        rs[it] = rstd;
+    }
+    __syncthreads();
+    // dgamma/dbeta partial sums over this block's tokens: one thread per (ni, head, j)
+    const int nn = ((norm_mask & 1) + ((norm_mask >> 1) & 1) + ((norm_mask >> 2) & 1));
+    const int hd = h * dk;
+    float* pg = partial + (int64_t)blockIdx.x * 2 * 2 * hd;
+    for (int e = threadIdx.x; e < 2 * hd; e += blockDim.x) {
+        const int ni = e / hd, head = (e % hd) / dk, j = e % dk;
+        float sg = 0.f, sb = 0.f;
+        if (ni < nn) {
+            int stream = -1, cnt = -1;
+            for (int q = 0; q < 3; ++q)
+                if ((norm_mask >> q) & 1) { if (++cnt == ni) { stream = q; break; } }
+            const int s = stream * h + head;
+            for (int tok = 0; tok < nt; ++tok) {
+                const float gyv = dy[(tok * S + s) * pitch + j];
+                sg += gyv * xs[(tok * S + s) * pitch + j];
+                sb += gyv;
+            }
+        }
+        pg[e] = first ? sg : pg[e] + sg;
+        pg[2 * hd + e] = first ? sb : pg[2 * hd + e] + sb;
+    }
+    for (int e = threadIdx.x; e < nt * d3; e += blockDim.x) {
+        const int tok = e / d3, f = e % d3, s = f / dk, j = f % dk, stream = s / h, head = s % h;
+        const int it = tok * S + s;
+        float g = dy[it * pitch + j];
+        if ((norm_mask >> stream) & 1) {
+            int ni = 0;
+            for (int q = 0; q < stream; ++q) ni += (norm_mask >> q) & 1;
+            const float gm = gamma[(ni * h + head) * dk + j];
+            g = rs[it] * (g * gm - m1[it] - xs[it * pitch + j] * m2[it]);
+        }
+        d_qkv[(int64_t)(t0 + tok) * d3 + f] = g;
+    }
+    }   // token groups
+}
+
+// ---- bandwidth-shaped head norm (dk % 4 == 0) ------------------------------------------------------
+// Thread layout: PT = 3h*G lanes per token (G = pow2 >= dk/4 lanes per head segment, one float4 each),
+// R = blockDim/PT tokens in flight per pass; a lane keeps its (segment, quarter) for the whole kernel, so
+// gamma/beta stay in registers and (backward) the affine gradients accumulate in registers.  Segment
+// statistics are G-lane shuffle reductions.  qkv / d_qkv move as aligned float4; the head tiles (offset by
+// the p coordinate columns) move as float2 when p is even, scalars otherwise.
+struct HeadGeom {
+    int T, h, dk, p, DP, norm_mask, G, PT, R, tpb;
+};
+
+__device__ __forceinline__ float group_sum(float v, int G) {
+    for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ void headnorm_fwd_v2_kernel(const float* __restrict__ qkv, const float* __restrict__ pos,
+                                       const float* __restrict__ gamma, const float* __restrict__ beta,
+                                       HeadGeom g, float eps, float* __restrict__ out,
+                                       float* __restrict__ stats) {
+    const int r = threadIdx.x / g.PT, l = threadIdx.x % g.PT;
+    if (r >= g.R) return;
+    const int seg = l / g.G, q = l % g.G, Q4 = g.dk >> 2;
+    const bool active = q < Q4;
+    const int stream = seg / g.h, head = seg % g.h;
+    const bool normed = (g.norm_mask >> stream) & 1;
+    const int ni = __popc(g.norm_mask & ((1 << stream) - 1));
+    f32x4 gm = {1.f, 1.f, 1.f, 1.f}, bt = {0.f, 0.f, 0.f, 0.f};
+    if (normed && active) {
+        gm = *reinterpret_cast<const f32x4*>(gamma + (ni * g.h + head) * g.dk + 4 * q);
+        bt = *reinterpret_cast<const f32x4*>(beta + (ni * g.h + head) * g.dk + 4 * q);
+    }
+    const int d3 = 3 * g.h * g.dk;
+    const float inv = 1.f / (float)g.dk;
+    const int t_end = min(g.T, (int)(blockIdx.x + 1) * g.tpb);
+    // two tokens per trip: both loads are requested before either is consumed
+    for (int t = blockIdx.x * g.tpb + r; t < t_end; t += 2 * g.R) {
+        const bool two = t + g.R < t_end;
+        f32x4 xx[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        if (active) {
+            xx[0] = *reinterpret_cast<const f32x4*>(qkv + (int64_t)t * d3 + seg * g.dk + 4 * q);
+            if (two) xx[1] = *reinterpret_cast<const f32x4*>(qkv + (int64_t)(t + g.R) * d3 + seg * g.dk + 4 * q);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            if (u == 1 && !two) break;
+            const int tt = t + u * g.R;
+            const f32x4 x = xx[u];
+            f32x4 y = x;
+            if (normed) {
+                const float mu = group_sum(x[0] + x[1] + x[2] + x[3], g.G) * inv;
+                f32x4 c = x - mu;
+                if (!active) c = f32x4{0.f, 0.f, 0.f, 0.f};
+                const float var = group_sum(c[0] * c[0] + c[1] * c[1] + c[2] * c[2] + c[3] * c[3], g.G) * inv;
+                const float rstd = 1.f / sqrtf(var + eps);
+                y = c * rstd * gm + bt;
+                if (q == 0)
+                    *reinterpret_cast<f32x2*>(stats + (((int64_t)ni * g.T + tt) * g.h + head) * 2) = f32x2{mu, rstd};
+            }
+            float* row = out + (((int64_t)stream * g.T + tt) * g.h + head) * g.DP;
+            if (active) tile_store4(row + g.p + 4 * q, g.p, y);
+            if (q == 0)
+                for (int j = 0; j < g.p; ++j) row[j] = pos[(int64_t)tt * g.p + j];
+            if (q == Q4 - 1)
+                for (int j = g.p + g.dk; j < g.DP; ++j) row[j] = 0.f;
+        }
+    }
+}
+
+__global__ void headnorm_bwd_v2_kernel(const float* __restrict__ d_out, const float* __restrict__ qkv,
+                                       const float* __restrict__ gamma, const float* __restrict__ stats,
+                                       HeadGeom g, float* __restrict__ d_qkv,
+                                       float* __restrict__ partial /* [nblk][dg: 2*h*dk | db: 2*h*dk] */) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];      // [R][PT][8]
+    const int r = threadIdx.x / g.PT, l = threadIdx.x % g.PT;
+    const int hd = g.h * g.dk;
+    if (r < g.R) {
+        const int seg = l / g.G, q = l % g.G, Q4 = g.dk >> 2;
+        const bool active = q < Q4;
+        const int stream = seg / g.h, head = seg % g.h;
+        const bool normed = (g.norm_mask >> stream) & 1;
+        const int ni = __popc(g.norm_mask & ((1 << stream) - 1));
+        f32x4 gm = {1.f, 1.f, 1.f, 1.f};
+        if (normed && active) gm = *reinterpret_cast<const f32x4*>(gamma + (ni * g.h + head) * g.dk + 4 * q);
+        f32x4 dg = {0.f, 0.f, 0.f, 0.f}, db = {0.f, 0.f, 0.f, 0.f};
+        const int d3 = 3 * hd;
+        const float inv = 1.f / (float)g.dk;
+        const int t_end = min(g.T, (int)(blockIdx.x + 1) * g.tpb);
+        for (int t = blockIdx.x * g.tpb + r; t < t_end; t += 2 * g.R) {      // two tokens per trip (see forward)
+            const bool two = t + g.R < t_end;
+            f32x4 gyy[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, xx[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+            f32x2 stt[2] = {{0.f, 0.f}, {0.f, 0.f}};
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                if (u == 1 && !two) break;
+                const int tt = t + u * g.R;
+                if (active) {
+                    gyy[u] = tile_load4(d_out + (((int64_t)stream * g.T + tt) * g.h + head) * g.DP + g.p + 4 * q, g.p);
+                    if (normed) xx[u] = *reinterpret_cast<const f32x4*>(qkv + (int64_t)tt * d3 + seg * g.dk + 4 * q);
+                }
+                if (normed) stt[u] = *reinterpret_cast<const f32x2*>(stats + (((int64_t)ni * g.T + tt) * g.h + head) * 2);
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                if (u == 1 && !two) break;
+                const int tt = t + u * g.R;
+                const f32x4 gy = gyy[u], x = xx[u];
+                f32x4 dx = gy;
+                if (normed) {
+                    const float mu = stt[u][0], rstd = stt[u][1];
+                    f32x4 xh = (x - mu) * rstd;
+                    if (!active) xh = f32x4{0.f, 0.f, 0.f, 0.f};
+                    const f32x4 gg = gy * gm;
+                    const float m1 = group_sum(gg[0] + gg[1] + gg[2] + gg[3], g.G) * inv;
+                    const float m2 = group_sum(gg[0] * xh[0] + gg[1] * xh[1] + gg[2] * xh[2] + gg[3] * xh[3], g.G) * inv;
+                    dx = rstd * (gg - m1 - xh * m2);
+                    dg += gy * xh;
+                    db += gy;
+                }
+                if (active) *reinterpret_cast<f32x4*>(d_qkv + (int64_t)tt * d3 + seg * g.dk + 4 * q) = dx;
+            }
+        }
+        float* me = lds + ((size_t)r * g.PT + l) * 8;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { me[j] = dg[j]; me[4 + j] = db[j]; }
+    }
+    __syncthreads();
+    // fixed-order combine over the R token rows, one thread per (lane slot, component)
+    float* pg = partial + (int64_t)blockIdx.x * 4 * hd;
+    const int nn = __popc(g.norm_mask & 7);
+    for (int e = threadIdx.x; e < 4 * hd; e += blockDim.x)          // slots of absent norm streams
+        if ((e % (2 * hd)) / hd >= nn) pg[e] = 0.f;
+    for (int e = threadIdx.x; e < g.PT * 8; e += blockDim.x) {
+        const int ll = e >> 3, comp = e & 7;
+        const int seg = ll / g.G, q = ll % g.G;
+        const int stream = seg / g.h, head = seg % g.h;
+        if (q >= (g.dk >> 2) || !((g.norm_mask >> stream) & 1)) continue;
+        const int ni = __popc(g.norm_mask & ((1 << stream) - 1));
+        float s = 0.f;
+        for (int rr = 0; rr < g.R; ++rr) s += lds[((size_t)rr * g.PT + ll) * 8 + comp];
+        const int idx = ni * hd + head * g.dk + 4 * q + (comp & 3);
+        pg[(comp < 4 ? 0 : 2 * hd) + idx] = s;
+    }
+}
+
+static bool head_geom(int T, int h, int dk, int p, int norm_mask, int max_blocks, HeadGeom* g, int* threads,
+                      int* blocks) {
+    if (dk & 3) return false;
+    int G = 1;
+    while (G < dk / 4) G <<= 1;
+    if (G > 64) return false;
+    const int PT = 3 * h * G;
+    if (PT > 1024) return false;
+    // whole waves with no idle lanes when PT and the wave size have a small common multiple (PT = 96 -> 384)
+    int lcm = PT;
+    while (lcm % 64) lcm += PT;
+    int thr = lcm <= 512 ? lcm * std::max(1, 384 / lcm) : std::max(256, ((PT + 63) / 64) * 64);
+    const int R = thr / PT;
+    int nblk = std::min(max_blocks, ceil_div(T, R * 8));
+    nblk = std::max(nblk, 1);
+    int tpb = ceil_div(T, nblk);
+    tpb = ceil_div(tpb, R) * R;
+    nblk = ceil_div(T, tpb);
+    *g = HeadGeom{T, h, dk, p, (dk + p + 3) & ~3, norm_mask, G, PT, R, tpb};
+    *threads = thr;
+    *blocks = nblk;
+    return true;
+}
+
+static inline int hn_tok_bwd(int h, int dk) { return hn_tok(2 * 3 * h * (dk + 1) + 9 * h); }
+constexpr int HN_MAXB = 1024;      // bound on blocks (= dgamma/dbeta partials) of the backward
+static inline int hn_blocks_bwd(int T, int h, int dk) { return std::min(ceil_div(T, hn_tok_bwd(h, dk)), HN_MAXB); }
+
+}  // namespace gt
+
+using namespace gt;
+
+extern "C" int gt_headnorm_fwd(const float* qkv, const float* pos, const float* gamma, const float* beta,
+                               int32_t T, int32_t h, int32_t dk, int32_t p, int32_t norm_mask, float eps,
+                               float* out, float* stats, void* stream) {
+    if (!qkv || !out || T <= 0 || h <= 0 || dk <= 0 || p < 0) return GT_EINVAL;
+    if (p > 0 && !pos) return GT_EINVAL;
+    if (norm_mask & ~7) return GT_EINVAL;
+    if (norm_mask && (!gamma || !beta || !stats)) return GT_EINVAL;
+    const int DP = round4(dk + p);
+    HeadGeom g; int thr, nblk;
+    if (!misaligned16(qkv, out, gamma, beta, stats) && head_geom(T, h, dk, p, norm_mask, 1 << 20, &g, &thr, &nblk)) {
+        hipLaunchKernelGGL(headnorm_fwd_v2_kernel, dim3(nblk), dim3(thr), 0, (hipStream_t)stream, qkv, pos,
+                           gamma, beta, g, eps, out, stats);
+        GT_LAUNCH_CHECK();
+        return 0;
+    }
+    const int tok = hn_tok(3 * h * (dk + 1));
+    const size_t lds = (size_t)tok * 3 * h * (dk + 1) * sizeof(float);
+    if (lds > 64 * 1024) return GT_ENOTSUP;
+    hipLaunchKernelGGL(headnorm_fwd_kernel, dim3(ceil_div(T, tok)), dim3(256), lds, (hipStream_t)stream,
+                       qkv, pos, gamma, beta, T, h, dk, p, DP, norm_mask, eps, out, stats, tok);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int64_t gt_headnorm_bwd_ws_bytes(int32_t T, int32_t h, int32_t dk) {
+    (void)T;
+    return (int64_t)HN_MAXB * 4 * h * dk * (int64_t)sizeof(float);      // upper bound for both kernels
+}
+
+extern "C" int gt_headnorm_bwd(const float* d_out, const float* qkv, const float* gamma, const float* stats,
+                               int32_t T, int32_t h, int32_t dk, int32_t p, int32_t norm_mask, float* d_qkv,
+                               float* dgamma, float* dbeta, void* ws, int64_t ws_bytes, void* stream) {
+    if (!d_out || !qkv || !d_qkv || T <= 0 || h <= 0 || dk <= 0 || p < 0) return GT_EINVAL;
+    if (norm_mask & ~7) return GT_EINVAL;
+    if (norm_mask && (!gamma || !stats || !dgamma || !dbeta)) return GT_EINVAL;
+    if (!ws || ws_bytes < gt_headnorm_bwd_ws_bytes(T, h, dk)) return GT_EWS;
+    const int DP = round4(dk + p);
+    const int S = 3 * h;
+    const int tok = hn_tok_bwd(h, dk);
+    const size_t lds = ((size_t)2 * tok * S * (dk + 1) + 3 * tok * S) * sizeof(float);
+    int nblk = hn_blocks_bwd(T, h, dk);
+    float* partial = reinterpret_cast<float*>(ws);
+    HeadGeom g; int thr, nb2;
+    if (!misaligned16(qkv, d_qkv, gamma, stats, d_out) && head_geom(T, h, dk, p, norm_mask, HN_MAXB, &g, &thr, &nb2)) {
+        nblk = nb2;
+        const size_t lds2 = (size_t)g.R * g.PT * 8 * sizeof(float);
+        hipLaunchKernelGGL(headnorm_bwd_v2_kernel, dim3(nblk), dim3(thr), lds2, (hipStream_t)stream, d_out,
+                           qkv, gamma, stats, g, d_qkv, partial);
+    } else {
+        if (lds > 64 * 1024) return GT_ENOTSUP;
+        hipLaunchKernelGGL(headnorm_bwd_kernel, dim3(nblk), dim3(256), lds, (hipStream_t)stream, d_out, qkv,
+                           gamma, stats, T, h, dk, p, DP, norm_mask, d_qkv, partial, tok);
+    }
+    GT_LAUNCH_CHECK();
+    if (norm_mask) {
+        const int hd = h * dk;
+        // partial: [nblk][ (dg: 2*hd) | (db: 2*hd) ]
+        if (int rc = gt_slab_reduce(partial, 4 * hd, nblk, 2 * hd, 1.f, dgamma, stream)) return rc;
+        return gt_slab_reduce(partial + 2 * hd, 4 * hd, nblk, 2 * hd, 1.f, dbeta, stream);
+    }
+    return 0;
+}

@@ -319,16 +319,13 @@ __global__ __launch_bounds__(TS_THREADS) void token_softmax_apply_kernel(TsP p) 
 static inline bool linattn_shape_ok(int dk, int p) {
     return (dk == 16 || dk == 32 || dk == 48 || dk == 64 || dk == 96) && p >= 0 && p <= 2;
 }
-static inline bool misaligned(const void* a, const void* b = nullptr, const void* c = nullptr) {
-    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) != 0;
-}
 
 template <bool BWD>
 int token_softmax_run(const float* X, const float* G, float* Y, int B, int n, int h, int dk, int pd, void* ws,
                       int64_t ws_bytes, void* stream) {
     if (!X || !Y || (BWD && !G) || B <= 0 || n <= 0 || h <= 0) return GT_EINVAL;
     if (!linattn_shape_ok(dk, pd) || B > 65535) return GT_ENOTSUP;
-    if (misaligned(X, G, Y) || misaligned(ws)) return GT_EALIGN;
+    if (misaligned16(X, G, Y, ws)) return GT_EALIGN;
     if (!ws || ws_bytes < gt_token_softmax_ws_bytes(B, n, h, dk, pd)) return GT_EWS;
     const int Dr = dk + pd, DP = (Dr + 3) & ~3;
     const TsGeom g = ts_geom(n, h, DP);
@@ -351,7 +348,7 @@ using namespace gt;
 extern "C" int gt_feature_softmax_fwd(const float* X, float* Y, int64_t rows, int32_t dk, int32_t p, void* stream) {
     if (!X || !Y || rows <= 0) return GT_EINVAL;
     if (!linattn_shape_ok(dk, p)) return GT_ENOTSUP;
-    if (misaligned(X, Y)) return GT_EALIGN;
+    if (misaligned16(X, Y)) return GT_EALIGN;
     const int Dr = dk + p, L4 = ((Dr + 3) & ~3) / 4, S = fs_segments(L4);
     const int64_t nblk = (rows + S - 1) / S;
     if (nblk > 0x7fffffff) return GT_ENOTSUP;
@@ -365,7 +362,7 @@ extern "C" int gt_feature_softmax_bwd(const float* Y, const float* dY, float* dX
                                       void* stream) {
     if (!Y || !dY || !dX || rows <= 0) return GT_EINVAL;
     if (!linattn_shape_ok(dk, p)) return GT_ENOTSUP;
-    if (misaligned(Y, dY, dX)) return GT_EALIGN;
+    if (misaligned16(Y, dY, dX)) return GT_EALIGN;
     const int Dr = dk + p, L4 = ((Dr + 3) & ~3) / 4, S = fs_segments(L4);
     const int64_t nblk = (rows + S - 1) / S;
     if (nblk > 0x7fffffff) return GT_ENOTSUP;

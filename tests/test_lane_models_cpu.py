@@ -20,7 +20,7 @@ def test_mfma_model_selftest():
 
 @pytest.mark.parametrize("G,n", [(1, 21), (2, 37), (3, 16)])
 def test_galerkin_dkv_lane_map(G, n):
-    """galerkin_dkv_kernel<G> (gt_ops.hip): dK' = V' dM^T, dV' = K' dM for one (batch, head)."""
+    """galerkin_dkv_kernel<G> (gt_galerkin.hip): dK' = V' dM^T, dV' = K' dM for one (batch, head)."""
     DP, NS, NMT = 16 * G + 4, 4 * G + 1, G + 1
     rng = np.random.default_rng(G)
     K, V, dM = rng.standard_normal((n, DP)), rng.standard_normal((n, DP)), rng.standard_normal((DP, DP))
@@ -252,7 +252,7 @@ def test_dft_analysis_lane_map(n, P):
 
 @pytest.mark.parametrize("G,n,p", [(2, 37, 2), (1, 21, 2), (2, 40, 1), (3, 18, 2)])
 def test_galerkin_dkv_ln_plain_lane_map(G, n, p):
-    """galerkin_dkv_ln_kernel<G, PLAIN = true> (gt_ops.hip) for one (batch, head): output columns in value order (a row
+    """galerkin_dkv_ln_kernel<G, PLAIN = true> (gt_galerkin.hip) for one (batch, head): output columns in value order (a row
     permutation of the dM fragments), gamma folded into the fragment rows, beta dM as the accumulators' start value, the
     LayerNorm backward on the lanes that hold the products (row means over the four kq lanes of a token), d(gamma) /
     d(beta) folded over the token lanes -- against the plain numpy statement of the same backward."""

@@ -121,6 +121,16 @@ _PROTOS = {
     "gt_fourier16_attn": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.POINTER(GtDropout),
                                                                   C.c_int32, C.c_int32, C.c_void_p]),
     "gt_dropout_block16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(GtDropout), C.c_void_p]),
+    "gt_softmax_attn_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.POINTER(GtDropout),
+                                                                    C.c_void_p]),
+    "gt_softmax_attn_bwd_q": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.POINTER(GtDropout),
+                                                                      C.c_void_p]),
+    "gt_softmax_attn_bwd_kv": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.POINTER(GtDropout),
+                                                                       C.c_void_p]),
+    "gt_row_softmax_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(GtDropout),
+                                                         C.c_void_p]),
+    "gt_row_softmax_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(GtDropout),
+                                                         C.c_void_p]),
     "gt_dropact_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(GtDropout), C.c_int32, C.POINTER(GtDropout),
                                  C.c_int32, C.c_void_p]),
     "gt_dropact_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(GtDropout), C.c_int32,
@@ -1424,3 +1434,72 @@ def fourier_attn(F1, F2, T1, T2, B: int, n: int, h: int, DP: int, scale: float, 
                                                ptr(O2), B, n, h, DP, scale, ptr(mask), dp, int(owner_is_key),
                                                stream_ptr()), shape=(B, n, h, DP, nprod)), "gt_fourier_attn")
     return (O1, O2) if F2 is not None else O1
+
+
+# ----------------------------------------------------------------------------------- softmax attention (gt_softmax.hip)
+SOFTMAX_DP = FOURIER_DP       # head-tile widths of the fused softmax kernels: 16*NF + 4
+
+
+def _drop_ref(drop):
+    return C.byref(drop) if (drop is not None and drop.p > 0) else None
+
+
+def softmax_attn_fwd(Q, K, V, B: int, n: int, h: int, DP: int, scale: float, mask, drop, O=None, L=None):
+    """gt_softmax_attn_fwd on head tiles [B*n, h, DP]: returns (O, L), L [2, B, h, n]: L[0] = row maximum + log row sum,
+    L[1] its rounding residual (gt_hip.h)."""
+    need_f32_cuda(Q, K, V, mask, O, L)
+    if O is None:
+        O = torch.empty(B * n, h, DP, dtype=torch.float32, device=Q.device)
+    if L is None:
+        L = torch.empty(2, B, h, n, dtype=torch.float32, device=Q.device)
+    check(_timed("gt_softmax_attn_fwd", 4.0 * B * h * n * n * DP, 16.0 * B * n * h * DP,
+                 lambda: lib().gt_softmax_attn_fwd(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), B, n,
+                                                   h, DP, scale, ptr(mask), _drop_ref(drop), stream_ptr()),
+                 shape=(B, n, h, DP)), "gt_softmax_attn_fwd")
+    return O, L
+
+
+def softmax_attn_bwd(dO, O, Q, K, V, L, B: int, n: int, h: int, DP: int, scale: float, mask, drop, dQ=None, dK=None,
+                     dV=None):
+    """gt_softmax_attn_bwd_q, then gt_softmax_attn_bwd_kv (which reads the D of the first): returns (dQ, dK, dV, D)."""
+    need_f32_cuda(dO, O, Q, K, V, L, mask, dQ, dK, dV)
+    dev = Q.device
+    dQ, dK, dV = (torch.empty(B * n, h, DP, dtype=torch.float32, device=dev) if t is None else t for t in (dQ, dK, dV))
+    D = torch.empty(B, h, n, dtype=torch.float32, device=dev)
+    check(_timed("gt_softmax_attn_bwd_q", 6.0 * B * h * n * n * DP, 24.0 * B * n * h * DP,
+                 lambda: lib().gt_softmax_attn_bwd_q(dO.data_ptr(), O.data_ptr(), Q.data_ptr(), K.data_ptr(), V.data_ptr(),
+                                                     L.data_ptr(), D.data_ptr(), dQ.data_ptr(), B, n, h, DP, scale, ptr(mask),
+                                                     _drop_ref(drop), stream_ptr()), shape=(B, n, h, DP)),
+          "gt_softmax_attn_bwd_q")
+    check(_timed("gt_softmax_attn_bwd_kv", 8.0 * B * h * n * n * DP, 24.0 * B * n * h * DP,
+                 lambda: lib().gt_softmax_attn_bwd_kv(K.data_ptr(), V.data_ptr(), Q.data_ptr(), dO.data_ptr(), L.data_ptr(),
+                                                      D.data_ptr(), dK.data_ptr(), dV.data_ptr(), B, n, h, DP, scale,
+                                                      ptr(mask), _drop_ref(drop), stream_ptr()), shape=(B, n, h, DP)),
+          "gt_softmax_attn_bwd_kv")
+    return dQ, dK, dV, D
+
+
+def row_softmax_fwd(S, rows: int, n: int, mask, drop, P=None, Pm=None, row0: int = 0):
+    """gt_row_softmax_fwd on a dense [rows, n] score matrix: returns (P, Pm); without mask and dropout Pm is P."""
+    need_f32_cuda(S, mask, P, Pm)
+    assert S.is_contiguous() and S.numel() == rows * n
+    if P is None:
+        P = torch.empty_like(S)
+    if Pm is None:
+        Pm = torch.empty_like(S) if (mask is not None or _drop_ref(drop) is not None) else P
+    check(_timed("gt_row_softmax_fwd", 0.0, 12.0 * S.numel(),
+                 lambda: lib().gt_row_softmax_fwd(S.data_ptr(), P.data_ptr(), Pm.data_ptr(), rows, n, row0, ptr(mask),
+                                                  _drop_ref(drop), stream_ptr())), "gt_row_softmax_fwd")
+    return P, Pm
+
+
+def row_softmax_bwd(P, dPm, rows: int, n: int, mask, drop, dS=None, row0: int = 0):
+    """gt_row_softmax_bwd: dS = P .* (m .* dPm - sum_k P m dPm); ``dS`` may be ``dPm``."""
+    need_f32_cuda(P, dPm, mask, dS)
+    assert P.is_contiguous() and dPm.is_contiguous() and P.numel() == rows * n
+    if dS is None:
+        dS = torch.empty_like(P)
+    check(_timed("gt_row_softmax_bwd", 0.0, 12.0 * P.numel(),
+                 lambda: lib().gt_row_softmax_bwd(P.data_ptr(), dPm.data_ptr(), dS.data_ptr(), rows, n, row0, ptr(mask),
+                                                  _drop_ref(drop), stream_ptr())), "gt_row_softmax_bwd")
+    return dS

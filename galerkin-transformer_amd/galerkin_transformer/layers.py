@@ -29,6 +29,7 @@ def default(value, d):
 
 _LINEAR_FAMILY = ("linear", "galerkin", "global")
 _HIP_ATTENTION = ("galerkin", "fourier", "integral", "local", "linear", "global")
+_SOFTMAX_ATTENTION = ("softmax",)      # on the HIP path too, with coordinates only (SimpleAttention.fused_forward)
 
 
 def _act_module(name, fallback="silu"):
@@ -331,11 +332,14 @@ class SimpleAttention(nn.Module):
     """Softmax-free attention with per-head LayerNorm and coordinate concatenation.
 
     Same parameters / state_dict keys as the reference (layers.py:793-828): ``linears.{0,1,2}``,
-    ``norm_K.{i}``, ``norm_V.{i}`` (galerkin) or ``norm_Q.{i}`` (fourier), ``fc``.  The HIP path covers
-    self-attention (query is key is value) of the 'galerkin', 'linear' / 'global' and 'fourier' ('integral', 'local')
-    types with norm_type='layer', and the Galerkin family with norm_type='instance': ``norm_K`` / ``norm_V`` are then
+    ``norm_K.{i}``, ``norm_V.{i}`` (galerkin) or ``norm_Q.{i}`` (fourier, softmax), ``fc``.  The HIP path covers
+    self-attention (query is key is value) of the 'galerkin', 'linear' / 'global', 'fourier' ('integral', 'local') and
+    'softmax' types with norm_type='layer', and the Galerkin family with norm_type='instance': ``norm_K`` / ``norm_V`` are then
     ``nn.InstanceNorm1d(d_k, affine=True)`` per head (same keys and shapes, no buffers) and K, V are normalised over the
     tokens, one mean and variance per (sample, head, channel), before the coordinates are concatenated (layers.py:842-854).
+    'softmax' (scaled dot-product attention, the dropout mask on the softmax output; fp32 arithmetic in every precision
+    mode) needs coordinates: head tiles of width round4(d_k + pos_dim) in {20, 36, 52}, i.e. d_k in (16, 32, 48) with
+    pos_dim >= 1; the coordinate-free call (``pos is None`` or ``pos_dim == 0``) raises NotImplementedError.
     Other variants of the reference are baselines outside the hot path."""
 
     def __init__(self, n_head, d_model, pos_dim: int = 1, attention_type="fourier", dropout=0.1,
@@ -426,10 +430,13 @@ class SimpleAttention(nn.Module):
 
     def fused_forward(self, x, pos=None, residual=None, sign=1.0, p_out=0.0, need_weights=True):
         """res + sign*dropout(attention(x)); the encoder layer's entry point.  ``need_weights=False`` lets the
-        Fourier type run fused (no n x n matrix in HBM; the returned weight is None)."""
-        if self.attention_type not in _HIP_ATTENTION:
+        Fourier and softmax types run fused (no n x n matrix in HBM; the returned weight is None)."""
+        if self.attention_type in _SOFTMAX_ATTENTION and (pos is None or self.pos_dim == 0):
+            raise NotImplementedError("attention_type='softmax' without coordinates is outside the HIP hot path: the softmax "
+                                      "kernels take head tiles of width 16*k + 4 (d_k in (16, 32, 48) plus pos_dim >= 1)")
+        if self.attention_type not in _HIP_ATTENTION + _SOFTMAX_ATTENTION:
             raise NotImplementedError(f"attention_type={self.attention_type!r} is outside the HIP hot path "
-                                      "(galerkin / fourier / linear only)")
+                                      "(galerkin / fourier / linear / softmax only)")
         use_pos = pos is not None and self.pos_dim > 0
         if use_pos:
             assert pos.size(-1) == self.pos_dim
@@ -448,6 +455,8 @@ class SimpleAttention(nn.Module):
             kind = "galerkin"
         elif self.attention_type in ("linear", "global"):     # the reference treats the two names alike (layers.py:719)
             kind = "linear"
+        elif self.attention_type in _SOFTMAX_ATTENTION:
+            kind = "softmax"
         else:
             kind = "fourier"
         out, w = ops.simple_attention(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc,

@@ -256,7 +256,7 @@ class _ConfiguredModel(nn.Module):
     """Config-dict plumbing shared by the three model classes: every config key (and every name in
     ADDITIONAL_ATTR) becomes an attribute, missing keys read as None (model.py:1071-1074)."""
 
-    _hip_attention = ('fourier', 'integral', 'local', 'galerkin', 'linear', 'global')
+    _hip_attention = ('fourier', 'integral', 'local', 'galerkin', 'linear', 'global', 'softmax')
 
     def _read_config(self, kwargs):
         self.config = defaultdict(lambda: None, **kwargs)
@@ -270,7 +270,7 @@ class _ConfiguredModel(nn.Module):
 
     def _stack_encoders(self, **extra):
         if self.attention_type not in self._hip_attention:
-            raise NotImplementedError(f"attention_type={self.attention_type!r}: only the galerkin / fourier / linear "
+            raise NotImplementedError(f"attention_type={self.attention_type!r}: only the galerkin / fourier / linear / softmax "
                                       "encoders are on the HIP hot path")
         layer = SimpleTransformerEncoderLayer(
             d_model=self.n_hidden, n_head=self.n_head, attention_type=self.attention_type,

@@ -1332,30 +1332,93 @@ def _fourier_bwd(s, g, d_attn, dims, sign, hbf, flash, f16, block16):
     return dO3, dwfc, dbfc
 
 
+def _softmax_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn, d_out, dims, sign, need_w):
+    """softmax core: P = softmax(Q' K'^T / sqrt(d_k')), out = res + sign * dropout(fc((P .* mask) V')), fused (gt_softmax_attn_*:
+    no n x n matrix in HBM) or, when the weights are wanted, materialised (gt_gemm + gt_row_softmax_*).  The attention runs in
+    fp32 on both routes in every precision mode; the fc product follows set_precision.  Returns (attn_weight = P .* mask,
+    tensors to save, flash): the route, decided once here; the backward follows it."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    T, hD, dev = B * n, h * DP, out.device
+    scale = 1.0 / math.sqrt(Dr)
+    wpad = torch.zeros(d, h, DP, dtype=torch.float32, device=dev)
+    wpad[:, :, :Dr] = wf.reshape(d, h, Dr)
+    wpad = wpad.reshape(d, hD)
+    flash = not need_w
+    P = Pm = L = None
+    if flash:
+        att, L = H.softmax_attn_fwd(Qp, Kp, Vp, B, n, h, DP, scale, mask, d_attn)
+        att = att.reshape(T, hD)
+    else:
+        P = torch.empty(B, h, n, n, dtype=torch.float32, device=dev)
+        H.gemm(Qp, Kp, P, n, n, DP, lda=hD, ldb=hD, ldc=n, batch=(B, h), a_bs=(n * hD, DP), b_bs=(n * hD, DP),
+               c_bs=(h * n * n, n * n), alpha=scale, precision="f32")
+        P, Pm = H.row_softmax_fwd(P, B * h * n, n, mask, d_attn, P=P)      # in place; Pm is P without mask and dropout
+        att = torch.empty(T, hD, dtype=torch.float32, device=dev)
+        H.gemm(Pm, Vp, att, n, DP, n, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=(h * n * n, n * n),
+               b_bs=(n * hD, DP), c_bs=(n * hD, DP), precision="f32")
+    H.gemm(att, wpad, out, T, d, hD, lda=hD, ldb=hD, ldc=d, bias=bfc, drop=d_out, res=rc, ldr=d, out_scale=sign)
+    attn_w = Pm if Pm is not None else torch.empty(0, device=dev)
+    return attn_w, dict(wpad=wpad, att=att, L=L, P=P, Pm=Pm), flash
+
+
+def _softmax_bwd(s, g, d_attn, dims, sign, hbf, flash):
+    """Backward of _softmax_fwd on the route it took.  Returns (dO3, dwfc, dbfc)."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    T, hD, dev = B * n, h * DP, g.device
+    dO3 = torch.empty(3, T, h, DP, dtype=torch.float32, device=dev)
+    Qp, Kp, Vp = s.out3[0], s.out3[1], s.out3[2]
+    scale = 1.0 / math.sqrt(Dr)
+    dwpad = torch.empty(d, hD, dtype=torch.float32, device=dev)
+    dbfc = torch.empty(d, dtype=torch.float32, device=dev) if hbf else None
+    H.gemm(g, s.att, dwpad, d, hD, T, layout_a=1, layout_b=1, lda=d, ldb=hD, ldc=hD, split_k=0, alpha=sign,
+           a_colsum=dbfc, a_drop_sign=sign)     # (alpha signs the product, a_drop_sign the column sums)
+    dwfc = dwpad.reshape(d, h, DP)[:, :, :Dr].reshape(d, h * Dr)
+    datt = torch.empty(T, hD, dtype=torch.float32, device=dev)
+    H.gemm(g, s.wpad, datt, T, hD, d, layout_b=1, lda=d, ldb=hD, ldc=hD, alpha=sign)
+    if flash:     # dQ' (and D), then dK', dV': P = exp(S - L) recomputed tile by tile
+        H.softmax_attn_bwd(datt.reshape(T, h, DP), s.att.reshape(T, h, DP), Qp, Kp, Vp, s.L, B, n, h, DP, scale, s.mask,
+                           d_attn, dQ=dO3[0], dK=dO3[1], dV=dO3[2])
+    else:
+        nn_bs = (h * n * n, n * n)
+        dS = torch.empty(B, h, n, n, dtype=torch.float32, device=dev)
+        H.gemm(datt, Vp, dS, n, n, DP, lda=hD, ldb=hD, ldc=n, batch=(B, h), a_bs=(n * hD, DP), b_bs=(n * hD, DP),
+               c_bs=nn_bs, precision="f32")                                # dPm = dO V'^T
+        H.row_softmax_bwd(s.P, dS, B * h * n, n, s.mask, d_attn, dS=dS)     # dS = P .* (m .* dPm - sum P m dPm), in place
+        # dV' = Pm^T datt ; dQ' = dS K' / sqrt(d_k') ; dK' = dS^T Q' / sqrt(d_k')
+        H.gemm(s.Pm, datt, dO3[2], n, DP, n, layout_a=1, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs,
+               b_bs=(n * hD, DP), c_bs=(n * hD, DP), precision="f32")
+        H.gemm(dS, Kp, dO3[0], n, DP, n, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs,
+               b_bs=(n * hD, DP), c_bs=(n * hD, DP), alpha=scale, precision="f32")
+        H.gemm(dS, Qp, dO3[1], n, DP, n, layout_a=1, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs,
+               b_bs=(n * hD, DP), c_bs=(n * hD, DP), alpha=scale, precision="f32")
+    return dO3, dwfc, dbfc
+
+
 class SimpleAttentionFn(Function):
     """out = res + sign * dropout1( fc( merge_heads( attention(Q', K', V') ) ) ).
 
     galerkin: per-head LN on K,V; M = mask .* (K'^T V')/n; heads: Q' M      (layers.py:708-734)
     linear  : the same on Q~ = softmax(Q', dim=-1), K~ = softmax(K', dim=-2)  (layers.py:719-722; 'global' too)
     fourier : per-head LN on Q,K; S = mask .* (Q' K'^T)/sqrt(d_k')/n; heads: S V' (layers.py:672-705)
+    softmax : per-head LN on Q,K; P = softmax(Q' K'^T/sqrt(d_k')); heads: (mask .* P) V'  (layers.py:691-703)
     with X' = [pos, X] per head (layers.py:869-874) and fc over the merged heads (layers.py:894-897).
     token_norm (norm_type='instance', galerkin / linear): K, V are normalised over the TOKENS per (sample, head, channel)
     instead (layers.py:842-854): the projection writes raw tiles, gt_token_norm_fwd normalises their value columns.
     Also returns the attention matrix (``attn_weight``), detached.
 
     One autograd node in two stages.  forward: _project_heads (QKV projection, head norm, token norm; shared), then the core
-    of the kind, _galerkin_fwd (galerkin, linear) or _fourier_fwd, which ends in the fc product that writes ``out``.
-    backward: _galerkin_bwd / _fourier_bwd, then _project_heads_bwd.  Forward to backward: the tensors go by name through
+    of the kind, _galerkin_fwd (galerkin, linear), _fourier_fwd or _softmax_fwd, which ends in the fc product that writes
+    ``out``.  backward: _galerkin_bwd / _fourier_bwd / _softmax_bwd, then _project_heads_bwd.  Forward to backward: the tensors go by name through
     _save_named / _saved; ctx.cfg, ctx.dims, ctx.salt, ctx.has (bqkv, bfc, res given), ctx.xshape and ctx.in_mask carry the
-    call; ctx.plain, ctx.fused_ln and, for fourier, ctx.flash, ctx.f16, ctx.block16 record every route the forward chose.
+    call; ctx.plain, ctx.fused_ln and, for fourier, ctx.flash, ctx.f16, ctx.block16 (softmax: ctx.flash) record every route the forward chose.
     The backward follows them and consults no module-level switch."""
 
     @staticmethod
     def forward(ctx, x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, cfg, mask):
         (kind, h, norm_mask, eps, sign, p_attn, p_out, need_w, token_norm) = cfg
-        if kind not in ("galerkin", "linear", "fourier"):
+        if kind not in ("galerkin", "linear", "fourier", "softmax"):
             raise ValueError(f"simple_attention: kind={kind!r}")
-        if token_norm and (kind == "fourier" or norm_mask != 0b110 or gamma is None or beta is None):
+        if token_norm and (kind in ("fourier", "softmax") or norm_mask != 0b110 or gamma is None or beta is None):
             raise ValueError("simple_attention: token_norm is the K, V norm of the galerkin / linear kinds")
         H.need_f32_cuda(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, mask)
         B, n, d = x.shape
@@ -1366,6 +1429,9 @@ class SimpleAttentionFn(Function):
         dev = x.device
         if kind == "linear" and not H.linattn_supported(dk, p):
             raise H.GtNotSupported(f"linear attention: head size d_k={dk}, pos_dim={p} has no softmax kernel")
+        if kind == "softmax" and DP not in H.SOFTMAX_DP:
+            raise H.GtNotSupported(f"softmax attention: head tile width round4(d_k + pos_dim) = {DP} has no kernel "
+                                   f"(supported: {H.SOFTMAX_DP}, i.e. d_k in (16, 32, 48) with 1..4 coordinate columns)")
         if token_norm:
             if n < 2:       # nn.InstanceNorm1d: "Expected more than 1 spatial element when training"
                 raise ValueError(f"norm_type='instance' needs more than 1 token per sample to normalise over (got n={n})")
@@ -1390,6 +1456,8 @@ class SimpleAttentionFn(Function):
         if kind in ("galerkin", "linear"):
             attn_w, core = _galerkin_fwd(kind, Qp, Kp, Vp, out, rc, wf, bfc, (gamma, beta) if plain else (None, None), mask,
                                          d_attn, d_out, dims, sign)
+        elif kind == "softmax":
+            attn_w, core, ctx.flash = _softmax_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn, d_out, dims, sign, need_w)
         else:
             attn_w, core, (ctx.flash, ctx.f16, ctx.block16) = _fourier_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn,
                                                                            d_out, dims, sign, need_w)
@@ -1421,6 +1489,8 @@ class SimpleAttentionFn(Function):
         if kind in ("galerkin", "linear"):
             dO3, ln, dwfc, dbfc = _galerkin_bwd(kind, s, g, d_attn, ctx.dims, sign, hbf, token_norm, ctx.plain,
                                                 ctx.fused_ln)
+        elif kind == "softmax":
+            dO3, dwfc, dbfc = _softmax_bwd(s, g, d_attn, ctx.dims, sign, hbf, ctx.flash)
         else:
             dO3, dwfc, dbfc = _fourier_bwd(s, g, d_attn, ctx.dims, sign, hbf, ctx.flash, ctx.f16, ctx.block16)
         dx, dwqkv, dbqkv, dgamma, dbeta = _project_heads_bwd(s, dO3, ln, g_in, ctx.in_mask, ctx.dims, norm_mask, token_norm,
@@ -1431,8 +1501,8 @@ class SimpleAttentionFn(Function):
 def simple_attention(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, *, kind: str, n_head: int, norm_mask: int,
                      eps: float, res=None, sign: float = 1.0, p_out: float = 0.0, need_weights: bool = True,
                      token_norm: bool = False):
-    """Self-attention block; ``res`` must be ``x`` (or None).  Returns (out, attn_weight).  For the Fourier
-    type ``need_weights=False`` selects the fused kernel that never materialises the n x n matrix
+    """Self-attention block; ``res`` must be ``x`` (or None).  Returns (out, attn_weight).  For the Fourier and softmax
+    types ``need_weights=False`` selects the fused kernel that never materialises the n x n matrix
     (attn_weight is then None); the Galerkin matrix is small and always returned.  ``token_norm`` (galerkin / linear with
     norm_mask = K, V): gamma / beta are the affine of the token-axis norm (norm_type='instance') instead of the LayerNorm's."""
     _check_res_is_x(res, x, "simple_attention")

@@ -60,7 +60,8 @@ def get_model_name(model='burgers', num_encoder_layers=4, n_hidden=96, attention
 def _common_args(parser, attention_default, ffn_dropout, encoder_dropout, decoder_dropout, gamma):
     a = parser.add_argument
     a('--attention-type', type=str, default=attention_default, metavar='attn_type',
-      help='encoder attention: fourier (integral, local) or galerkin (global) run on the HIP path')
+      help='encoder attention: fourier (integral, local), galerkin, linear (global) or softmax (with coordinates; head '
+           'tiles of d_k in (16, 32, 48) plus pos_dim) run on the HIP path')
     a('--xavier-init', type=float, default=0.01, metavar='xavier_init')
     a('--diagonal-weight', type=float, default=0.01, metavar='diagonal weight')
     a('--ffn-dropout', type=float, default=ffn_dropout, metavar='ffn_dropout')

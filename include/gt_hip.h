@@ -476,6 +476,43 @@ int gt_fourier16_attn(const void* F1, const void* F2, const void* T1, const void
 int gt_dropout_block16(float* S, int64_t BH, int32_t n, const gt_dropout* drop, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Softmax attention (layers.py:672-705, attention_type='softmax'; additive, same ABI) on the head-tile layout [B*n][h][DP]:
+ *     S = Q' K'^T * scale,  P = softmax(S, over the keys),  Pm = P .* m,  O = Pm V'
+ * m multiplies P AFTER the softmax and never enters the row sum: a stateless dropout (keep / (1 - p), mask index
+ * ((b*h+head)*n + query)*n + key, the index documented at gt_fourier_attn; one hash per element), an explicit [B,h,n,n] mask
+ * (which wins over `drop`), or 1.  fp32 (v_mfma_f32_16x16x4_f32, hardware exp2) in every precision mode.
+ *
+ * Fused route -- the n x n matrix is never written; gt_fourier_attn's kernel plus a running row maximum, a running row sum
+ * and a rescale.  Rows of the last stream tile at or beyond n are excluded from the maximum and the sum.
+ *     gt_softmax_attn_fwd      -> O, and L[0][b,h,q] = max_k S + log sum_k exp(S - max)         L: [2][B][h][n]
+ *                                 L[1] = the rounding residual of L[0], (max - L[0]) + log sum: the backward evaluates
+ *                                 exp((S - L[0]) - L[1]), so that scores of any size lose nothing through the statistic
+ *     gt_softmax_attn_bwd_q    -> dQ', and D[b,h,q] = sum_c dO[q,c] O[q,c]                     D: [B][h][n]
+ *     gt_softmax_attn_bwd_kv   -> dK', dV'   (reads the L of the forward and the D of bwd_q: call it after bwd_q)
+ * with P = exp(S - L) recomputed (the scale multiplies the finished sum in all three passes: their S are bit-identical),  dPm = dO V'^T,  dV' = Pm^T dO,  dS = P .* (m .* dPm - D),  dQ' = dS K' * scale,
+ * dK' = dS^T Q' * scale.  Zero pad columns of the inputs give exactly zero pad columns in dQ', dK', dV'.
+ * DP in {20, 36, 52}, else GT_ENOTSUP.  Tiles and outputs 16-byte aligned.  No atomics: bit-identical from run to run.
+ *
+ * Materialised route (the caller wants Pm back): S by gt_gemm, then one wave per row of the [rows][n] matrix:
+ *     gt_row_softmax_fwd       P = softmax(S) (maximum subtracted), Pm = P .* m;  P == S and (no mask, no dropout) Pm == P allowed
+ *     gt_row_softmax_bwd       dS = P .* (m .* dPm - sum_k P m dPm);  dS == dPm allowed
+ * Mask index of element (row, k): (row0 + row)*n + k -- with rows = B*h*n and row0 = 0 the index of the fused route, so both
+ * routes draw one mask; `mask` (explicit) is indexed row*n + k.
+ * ------------------------------------------------------------------------------------------- */
+int gt_softmax_attn_fwd(const float* Q, const float* K, const float* V, float* O, float* L, int32_t B, int32_t n, int32_t h,
+                        int32_t DP, float scale, const float* mask, const gt_dropout* drop, void* stream);
+int gt_softmax_attn_bwd_q(const float* dO, const float* O, const float* Q, const float* K, const float* V, const float* L,
+                          float* D, float* dQ, int32_t B, int32_t n, int32_t h, int32_t DP, float scale, const float* mask,
+                          const gt_dropout* drop, void* stream);
+int gt_softmax_attn_bwd_kv(const float* K, const float* V, const float* Q, const float* dO, const float* L, const float* D,
+                           float* dK, float* dV, int32_t B, int32_t n, int32_t h, int32_t DP, float scale, const float* mask,
+                           const gt_dropout* drop, void* stream);
+int gt_row_softmax_fwd(const float* S, float* P, float* Pm, int64_t rows, int32_t n, int64_t row0, const float* mask,
+                       const gt_dropout* drop, void* stream);
+int gt_row_softmax_bwd(const float* P, const float* dPm, float* dS, int64_t rows, int32_t n, int64_t row0, const float* mask,
+                       const gt_dropout* drop, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Truncated-DFT stages along the contiguous grid axis of SpectralConv2d (layers.py:1176 rfft2 and :1187
  * irfft2 restricted to the kept modes; the residual nn.Linear of :1128 / :1196 rides on the synthesis).
  * One batch item = one grid line; all tensors dense fp32:

@@ -45,6 +45,7 @@ struct SoftmaxP {
 
 constexpr int SM_TS = 64;        // stream rows per LDS tile
 constexpr int SM_OW = 32;        // owner rows per wave
+constexpr int SM_WIDE_KS = 17;   // DP >= 68: the wide instances (gt_softmax_attn_wide_*)
 constexpr float SM_LOG2E = 1.4426950408889634f;
 enum { SM_PLAIN = 0, SM_DROP = 1, SM_MASK = 2 };
 enum { SM_FWD = 0, SM_BWDQ = 1, SM_BWDKV = 2 };
@@ -59,8 +60,10 @@ __device__ __forceinline__ float sm_exp(float x) { return __builtin_amdgcn_exp2f
 // Head tiles are DP = 16*NF + 4 floats wide; LDS tile image [64][DP], linear in float4 granules (gt_fourier.hip).
 template <int KS, int PASS, int MODE>
 // Blocks per CU: the widest register budget at which no instance spills (d/dK',V' holds four fragment sets, two score tiles
-// and two accumulator sets: from DP = 36 on it takes the whole file, AGPRs included).
-__global__ __launch_bounds__(256, PASS == SM_BWDKV ? (KS > 5 ? 1 : 2) : (PASS == SM_BWDQ ? (KS > 9 ? 1 : 2) : (KS > 5 ? 2 : 3)))
+// and two accumulator sets: from DP = 36 on it takes the whole file, AGPRs included).  The wide instances stage 68 / 100 KiB
+// of stream tiles per block: at most two blocks fit a CU at DP = 68, one at DP = 100, so they are bounded at one and the
+// allocator is free to use AGPRs in every pass.
+__global__ __launch_bounds__(256, KS >= SM_WIDE_KS ? 1 : PASS == SM_BWDKV ? (KS > 5 ? 1 : 2) : (PASS == SM_BWDQ ? (KS > 9 ? 1 : 2) : (KS > 5 ? 2 : 3)))
 void softmax_core_kernel(const SoftmaxP p) {
     constexpr int DP = 4 * KS, NF = (DP - 4) / 16, XC = DP - 4, TILE = SM_TS * DP;
     constexpr bool TWO = PASS != SM_FWD;           // two score tiles (S and dPm)
@@ -370,7 +373,8 @@ static void softmax_launch(const SoftmaxP& p, dim3 grid, hipStream_t st) {
 #undef GT_SM
 }
 
-template <int PASS>
+// WIDE selects the instance set of the entry point: DP in {20, 36, 52} (gt_softmax_attn_*) or {68, 100} (gt_softmax_attn_wide_*).
+template <int PASS, bool WIDE>
 static int softmax_attn(SoftmaxP p, int32_t B, int32_t DP, const gt_dropout* drop, void* stream) {
     if (!p.F1 || !p.T1 || !p.T2 || !p.O1 || !p.L || B <= 0 || p.n <= 0 || p.h <= 0 || DP <= 0) return GT_EINVAL;
     if (PASS != SM_FWD && (!p.F2 || !p.D)) return GT_EINVAL;
@@ -384,11 +388,19 @@ static int softmax_attn(SoftmaxP p, int32_t B, int32_t DP, const gt_dropout* dro
     p.lplane = (int64_t)B * p.h * p.n;
     dim3 grid((unsigned)ceil_div(p.n, 4 * SM_OW), (unsigned)p.h, (unsigned)B);
     hipStream_t st = (hipStream_t)stream;
-    switch (DP) {
-        case 20: softmax_launch<5, PASS>(p, grid, st); break;
-        case 36: softmax_launch<9, PASS>(p, grid, st); break;
-        case 52: softmax_launch<13, PASS>(p, grid, st); break;
-        default: return GT_ENOTSUP;
+    if (WIDE) {
+        switch (DP) {
+            case 68: softmax_launch<17, PASS>(p, grid, st); break;
+            case 100: softmax_launch<25, PASS>(p, grid, st); break;
+            default: return GT_ENOTSUP;
+        }
+    } else {
+        switch (DP) {
+            case 20: softmax_launch<5, PASS>(p, grid, st); break;
+            case 36: softmax_launch<9, PASS>(p, grid, st); break;
+            case 52: softmax_launch<13, PASS>(p, grid, st); break;
+            default: return GT_ENOTSUP;
+        }
     }
     GT_LAUNCH_CHECK();
     return 0;
@@ -445,21 +457,43 @@ extern "C" int gt_softmax_attn_fwd(const float* Q, const float* K, const float* 
                                    int32_t h, int32_t DP, float scale, const float* mask, const gt_dropout* drop,
                                    void* stream) {
     SoftmaxP p{Q, nullptr, K, V, O, nullptr, nullptr, L, 0, nullptr, mask, DropDev{}, n, h, scale};
-    return softmax_attn<SM_FWD>(p, B, DP, drop, stream);
+    return softmax_attn<SM_FWD, false>(p, B, DP, drop, stream);
 }
 
 extern "C" int gt_softmax_attn_bwd_q(const float* dO, const float* O, const float* Q, const float* K, const float* V,
                                      const float* L, float* D, float* dQ, int32_t B, int32_t n, int32_t h, int32_t DP,
                                      float scale, const float* mask, const gt_dropout* drop, void* stream) {
     SoftmaxP p{Q, dO, K, V, dQ, nullptr, O, const_cast<float*>(L), 0, D, mask, DropDev{}, n, h, scale};
-    return softmax_attn<SM_BWDQ>(p, B, DP, drop, stream);
+    return softmax_attn<SM_BWDQ, false>(p, B, DP, drop, stream);
 }
 
 extern "C" int gt_softmax_attn_bwd_kv(const float* K, const float* V, const float* Q, const float* dO, const float* L,
                                       const float* D, float* dK, float* dV, int32_t B, int32_t n, int32_t h, int32_t DP,
                                       float scale, const float* mask, const gt_dropout* drop, void* stream) {
     SoftmaxP p{K, V, Q, dO, dV, dK, nullptr, const_cast<float*>(L), 0, const_cast<float*>(D), mask, DropDev{}, n, h, scale};
-    return softmax_attn<SM_BWDKV>(p, B, DP, drop, stream);
+    return softmax_attn<SM_BWDKV, false>(p, B, DP, drop, stream);
+}
+
+// The same three passes at DP = 68 / 100: entry points of their own, so that the narrow ones keep answering GT_ENOTSUP there.
+extern "C" int gt_softmax_attn_wide_fwd(const float* Q, const float* K, const float* V, float* O, float* L, int32_t B, int32_t n,
+                                        int32_t h, int32_t DP, float scale, const float* mask, const gt_dropout* drop,
+                                        void* stream) {
+    SoftmaxP p{Q, nullptr, K, V, O, nullptr, nullptr, L, 0, nullptr, mask, DropDev{}, n, h, scale};
+    return softmax_attn<SM_FWD, true>(p, B, DP, drop, stream);
+}
+
+extern "C" int gt_softmax_attn_wide_bwd_q(const float* dO, const float* O, const float* Q, const float* K, const float* V,
+                                          const float* L, float* D, float* dQ, int32_t B, int32_t n, int32_t h, int32_t DP,
+                                          float scale, const float* mask, const gt_dropout* drop, void* stream) {
+    SoftmaxP p{Q, dO, K, V, dQ, nullptr, O, const_cast<float*>(L), 0, D, mask, DropDev{}, n, h, scale};
+    return softmax_attn<SM_BWDQ, true>(p, B, DP, drop, stream);
+}
+
+extern "C" int gt_softmax_attn_wide_bwd_kv(const float* K, const float* V, const float* Q, const float* dO, const float* L,
+                                           const float* D, float* dK, float* dV, int32_t B, int32_t n, int32_t h, int32_t DP,
+                                           float scale, const float* mask, const gt_dropout* drop, void* stream) {
+    SoftmaxP p{K, V, Q, dO, dV, dK, nullptr, const_cast<float*>(L), 0, const_cast<float*>(D), mask, DropDev{}, n, h, scale};
+    return softmax_attn<SM_BWDKV, true>(p, B, DP, drop, stream);
 }
 
 static int row_softmax_check(const void* a, const void* b, int64_t rows, int32_t n, const gt_dropout* drop) {

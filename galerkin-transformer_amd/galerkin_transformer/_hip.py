@@ -127,6 +127,12 @@ _PROTOS = {
                                                                       C.c_void_p]),
     "gt_softmax_attn_bwd_kv": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.POINTER(GtDropout),
                                                                        C.c_void_p]),
+    "gt_softmax_attn_wide_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.POINTER(GtDropout),
+                                                                         C.c_void_p]),
+    "gt_softmax_attn_wide_bwd_q": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 4 + [C.c_float, C.c_void_p,
+                                                                           C.POINTER(GtDropout), C.c_void_p]),
+    "gt_softmax_attn_wide_bwd_kv": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 4 + [C.c_float, C.c_void_p,
+                                                                            C.POINTER(GtDropout), C.c_void_p]),
     "gt_row_softmax_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(GtDropout),
                                                          C.c_void_p]),
     "gt_row_softmax_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(GtDropout),
@@ -1438,6 +1444,13 @@ def fourier_attn(F1, F2, T1, T2, B: int, n: int, h: int, DP: int, scale: float, 
 
 # ----------------------------------------------------------------------------------- softmax attention (gt_softmax.hip)
 SOFTMAX_DP = FOURIER_DP       # head-tile widths of the fused softmax kernels: 16*NF + 4
+SOFTMAX_DP_WIDE = (68, 100)   # d_k = 64 / 96: the same kernels behind entry points of their own (gt_softmax_attn_wide_*)
+
+
+def _softmax_sym(DP: int, tail: str) -> str:
+    """Entry point of one fused softmax pass for a head tile DP wide (an unsupported DP goes to the narrow one, which
+    answers GT_ENOTSUP)."""
+    return ("gt_softmax_attn_wide_" if DP in SOFTMAX_DP_WIDE else "gt_softmax_attn_") + tail
 
 
 def _drop_ref(drop):
@@ -1445,37 +1458,40 @@ def _drop_ref(drop):
 
 
 def softmax_attn_fwd(Q, K, V, B: int, n: int, h: int, DP: int, scale: float, mask, drop, O=None, L=None):
-    """gt_softmax_attn_fwd on head tiles [B*n, h, DP]: returns (O, L), L [2, B, h, n]: L[0] = row maximum + log row sum,
-    L[1] its rounding residual (gt_hip.h)."""
+    """gt_softmax_attn_fwd (DP 68 / 100: gt_softmax_attn_wide_fwd) on head tiles [B*n, h, DP]: returns (O, L), L [2, B, h, n]:
+    L[0] = row maximum + log row sum, L[1] its rounding residual (gt_hip.h)."""
     need_f32_cuda(Q, K, V, mask, O, L)
     if O is None:
         O = torch.empty(B * n, h, DP, dtype=torch.float32, device=Q.device)
     if L is None:
         L = torch.empty(2, B, h, n, dtype=torch.float32, device=Q.device)
-    check(_timed("gt_softmax_attn_fwd", 4.0 * B * h * n * n * DP, 16.0 * B * n * h * DP,
-                 lambda: lib().gt_softmax_attn_fwd(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), B, n,
-                                                   h, DP, scale, ptr(mask), _drop_ref(drop), stream_ptr()),
-                 shape=(B, n, h, DP)), "gt_softmax_attn_fwd")
+    sym = _softmax_sym(DP, "fwd")
+    check(_timed(sym, 4.0 * B * h * n * n * DP, 16.0 * B * n * h * DP,
+                 lambda: getattr(lib(), sym)(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), B, n, h, DP,
+                                             scale, ptr(mask), _drop_ref(drop), stream_ptr()),
+                 shape=(B, n, h, DP)), sym)
     return O, L
 
 
 def softmax_attn_bwd(dO, O, Q, K, V, L, B: int, n: int, h: int, DP: int, scale: float, mask, drop, dQ=None, dK=None,
                      dV=None):
-    """gt_softmax_attn_bwd_q, then gt_softmax_attn_bwd_kv (which reads the D of the first): returns (dQ, dK, dV, D)."""
+    """gt_softmax_attn_bwd_q, then gt_softmax_attn_bwd_kv (which reads the D of the first; DP 68 / 100: the _wide_ pair):
+    returns (dQ, dK, dV, D)."""
     need_f32_cuda(dO, O, Q, K, V, L, mask, dQ, dK, dV)
     dev = Q.device
     dQ, dK, dV = (torch.empty(B * n, h, DP, dtype=torch.float32, device=dev) if t is None else t for t in (dQ, dK, dV))
     D = torch.empty(B, h, n, dtype=torch.float32, device=dev)
-    check(_timed("gt_softmax_attn_bwd_q", 6.0 * B * h * n * n * DP, 24.0 * B * n * h * DP,
-                 lambda: lib().gt_softmax_attn_bwd_q(dO.data_ptr(), O.data_ptr(), Q.data_ptr(), K.data_ptr(), V.data_ptr(),
-                                                     L.data_ptr(), D.data_ptr(), dQ.data_ptr(), B, n, h, DP, scale, ptr(mask),
-                                                     _drop_ref(drop), stream_ptr()), shape=(B, n, h, DP)),
-          "gt_softmax_attn_bwd_q")
-    check(_timed("gt_softmax_attn_bwd_kv", 8.0 * B * h * n * n * DP, 24.0 * B * n * h * DP,
-                 lambda: lib().gt_softmax_attn_bwd_kv(K.data_ptr(), V.data_ptr(), Q.data_ptr(), dO.data_ptr(), L.data_ptr(),
-                                                      D.data_ptr(), dK.data_ptr(), dV.data_ptr(), B, n, h, DP, scale,
-                                                      ptr(mask), _drop_ref(drop), stream_ptr()), shape=(B, n, h, DP)),
-          "gt_softmax_attn_bwd_kv")
+    sym_q, sym_kv = _softmax_sym(DP, "bwd_q"), _softmax_sym(DP, "bwd_kv")
+    check(_timed(sym_q, 6.0 * B * h * n * n * DP, 24.0 * B * n * h * DP,
+                 lambda: getattr(lib(), sym_q)(dO.data_ptr(), O.data_ptr(), Q.data_ptr(), K.data_ptr(), V.data_ptr(),
+                                               L.data_ptr(), D.data_ptr(), dQ.data_ptr(), B, n, h, DP, scale, ptr(mask),
+                                               _drop_ref(drop), stream_ptr()), shape=(B, n, h, DP)),
+          sym_q)
+    check(_timed(sym_kv, 8.0 * B * h * n * n * DP, 24.0 * B * n * h * DP,
+                 lambda: getattr(lib(), sym_kv)(K.data_ptr(), V.data_ptr(), Q.data_ptr(), dO.data_ptr(), L.data_ptr(),
+                                                D.data_ptr(), dK.data_ptr(), dV.data_ptr(), B, n, h, DP, scale,
+                                                ptr(mask), _drop_ref(drop), stream_ptr()), shape=(B, n, h, DP)),
+          sym_kv)
     return dQ, dK, dV, D
 
 

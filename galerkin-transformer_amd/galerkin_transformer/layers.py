@@ -338,8 +338,8 @@ class SimpleAttention(nn.Module):
     ``nn.InstanceNorm1d(d_k, affine=True)`` per head (same keys and shapes, no buffers) and K, V are normalised over the
     tokens, one mean and variance per (sample, head, channel), before the coordinates are concatenated (layers.py:842-854).
     'softmax' (scaled dot-product attention, the dropout mask on the softmax output; fp32 arithmetic in every precision
-    mode) needs coordinates: head tiles of width round4(d_k + pos_dim) in {20, 36, 52}, i.e. d_k in (16, 32, 48) with
-    pos_dim >= 1; the coordinate-free call (``pos is None`` or ``pos_dim == 0``) raises NotImplementedError.
+    mode) needs coordinates: head tiles of width round4(d_k + pos_dim) in {20, 36, 52, 68, 100}, i.e. d_k in (16, 32, 48, 64,
+    96) with pos_dim >= 1 (the shipped ex1 configuration, d_model 96 / one head, is the 100-wide one); the coordinate-free call (``pos is None`` or ``pos_dim == 0``) raises NotImplementedError.
     Other variants of the reference are baselines outside the hot path."""
 
     def __init__(self, n_head, d_model, pos_dim: int = 1, attention_type="fourier", dropout=0.1,
@@ -433,7 +433,7 @@ class SimpleAttention(nn.Module):
         Fourier and softmax types run fused (no n x n matrix in HBM; the returned weight is None)."""
         if self.attention_type in _SOFTMAX_ATTENTION and (pos is None or self.pos_dim == 0):
             raise NotImplementedError("attention_type='softmax' without coordinates is outside the HIP hot path: the softmax "
-                                      "kernels take head tiles of width 16*k + 4 (d_k in (16, 32, 48) plus pos_dim >= 1)")
+                                      "kernels take head tiles of width 16*k + 4 (d_k in (16, 32, 48, 64, 96) plus pos_dim >= 1)")
         if self.attention_type not in _HIP_ATTENTION + _SOFTMAX_ATTENTION:
             raise NotImplementedError(f"attention_type={self.attention_type!r} is outside the HIP hot path "
                                       "(galerkin / fourier / linear / softmax only)")

@@ -1334,9 +1334,10 @@ def _fourier_bwd(s, g, d_attn, dims, sign, hbf, flash, f16, block16):
 
 def _softmax_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn, d_out, dims, sign, need_w):
     """softmax core: P = softmax(Q' K'^T / sqrt(d_k')), out = res + sign * dropout(fc((P .* mask) V')), fused (gt_softmax_attn_*:
-    no n x n matrix in HBM) or, when the weights are wanted, materialised (gt_gemm + gt_row_softmax_*).  The attention runs in
-    fp32 on both routes in every precision mode; the fc product follows set_precision.  Returns (attn_weight = P .* mask,
-    tensors to save, flash): the route, decided once here; the backward follows it."""
+    no n x n matrix in HBM; gt_softmax_attn_wide_* at DP 68 / 100) or, when the weights are wanted, materialised (gt_gemm +
+    gt_row_softmax_*).  The attention runs in fp32 on both routes in every precision mode; the fc product follows
+    set_precision.  Returns (attn_weight = P .* mask, tensors to save, flash): the route, decided once here; the backward
+    follows it."""
     B, n, d, h, dk, p, Dr, DP = dims
     T, hD, dev = B * n, h * DP, out.device
     scale = 1.0 / math.sqrt(Dr)
@@ -1429,9 +1430,10 @@ class SimpleAttentionFn(Function):
         dev = x.device
         if kind == "linear" and not H.linattn_supported(dk, p):
             raise H.GtNotSupported(f"linear attention: head size d_k={dk}, pos_dim={p} has no softmax kernel")
-        if kind == "softmax" and DP not in H.SOFTMAX_DP:
+        if kind == "softmax" and DP not in H.SOFTMAX_DP + H.SOFTMAX_DP_WIDE:
             raise H.GtNotSupported(f"softmax attention: head tile width round4(d_k + pos_dim) = {DP} has no kernel "
-                                   f"(supported: {H.SOFTMAX_DP}, i.e. d_k in (16, 32, 48) with 1..4 coordinate columns)")
+                                   f"(supported: {H.SOFTMAX_DP} and {H.SOFTMAX_DP_WIDE}, i.e. d_k in (16, 32, 48, 64, 96) "
+                                   f"with 1..4 coordinate columns)")
         if token_norm:
             if n < 2:       # nn.InstanceNorm1d: "Expected more than 1 spatial element when training"
                 raise ValueError(f"norm_type='instance' needs more than 1 token per sample to normalise over (got n={n})")

@@ -492,6 +492,9 @@ int gt_dropout_block16(float* S, int64_t BH, int32_t n, const gt_dropout* drop, 
  * with P = exp(S - L) recomputed (the scale multiplies the finished sum in all three passes: their S are bit-identical),  dPm = dO V'^T,  dV' = Pm^T dO,  dS = P .* (m .* dPm - D),  dQ' = dS K' * scale,
  * dK' = dS^T Q' * scale.  Zero pad columns of the inputs give exactly zero pad columns in dQ', dK', dV'.
  * DP in {20, 36, 52}, else GT_ENOTSUP.  Tiles and outputs 16-byte aligned.  No atomics: bit-identical from run to run.
+ *     gt_softmax_attn_wide_fwd / _wide_bwd_q / _wide_bwd_kv: the same three passes, arguments and contracts for the 64- and
+ *     96-wide heads, DP in {68, 100}, else GT_ENOTSUP (the narrow entry points keep returning GT_ENOTSUP at these widths).
+ *     One block per CU (68 / 100 KiB of LDS stream tiles per block).
  *
  * Materialised route (the caller wants Pm back): S by gt_gemm, then one wave per row of the [rows][n] matrix:
  *     gt_row_softmax_fwd       P = softmax(S) (maximum subtracted), Pm = P .* m;  P == S and (no mask, no dropout) Pm == P allowed
@@ -507,6 +510,14 @@ int gt_softmax_attn_bwd_q(const float* dO, const float* O, const float* Q, const
 int gt_softmax_attn_bwd_kv(const float* K, const float* V, const float* Q, const float* dO, const float* L, const float* D,
                            float* dK, float* dV, int32_t B, int32_t n, int32_t h, int32_t DP, float scale, const float* mask,
                            const gt_dropout* drop, void* stream);
+int gt_softmax_attn_wide_fwd(const float* Q, const float* K, const float* V, float* O, float* L, int32_t B, int32_t n,
+                             int32_t h, int32_t DP, float scale, const float* mask, const gt_dropout* drop, void* stream);
+int gt_softmax_attn_wide_bwd_q(const float* dO, const float* O, const float* Q, const float* K, const float* V, const float* L,
+                               float* D, float* dQ, int32_t B, int32_t n, int32_t h, int32_t DP, float scale,
+                               const float* mask, const gt_dropout* drop, void* stream);
+int gt_softmax_attn_wide_bwd_kv(const float* K, const float* V, const float* Q, const float* dO, const float* L,
+                                const float* D, float* dK, float* dV, int32_t B, int32_t n, int32_t h, int32_t DP, float scale,
+                                const float* mask, const gt_dropout* drop, void* stream);
 int gt_row_softmax_fwd(const float* S, float* P, float* Pm, int64_t rows, int32_t n, int64_t row0, const float* mask,
                        const gt_dropout* drop, void* stream);
 int gt_row_softmax_bwd(const float* P, const float* dPm, float* dS, int64_t rows, int32_t n, int64_t row0, const float* mask,

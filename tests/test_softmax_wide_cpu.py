@@ -1,0 +1,137 @@
+"""attention_type='softmax' at the 64- and 96-wide heads (head tiles DP = 68, 100), CPU side: the plain-torch restatement
+(tests/_softmax_ref.py) against the fixtures recorded from the reference (tests/golden/softmax_wide/), its float32-vs-float64
+envelope, and the host-visible surface of the wide kernels (entry points, width tuples, the operator's gate).  No GPU needed."""
+import ctypes
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from _softmax_ref import grad_errors, ref_grads, run_ref
+from _softmax_wide_ref import SUB, WIDE_GOLDEN, WIDE_PARTS, wide_golden
+from _util import GOLDEN, rel_l2
+from test_softmax_attention_cpu import REF_TOL
+
+WIDE_SYMBOLS = ("gt_softmax_attn_wide_fwd", "gt_softmax_attn_wide_bwd_q", "gt_softmax_attn_wide_bwd_kv")
+
+
+@pytest.mark.parametrize("name", WIDE_GOLDEN)
+def test_restatement_matches_reference_golden(name):
+    """The bars of test_softmax_attention_cpu.py: REF_TOL on the output, 5 x REF_TOL on every gradient."""
+    g = wide_golden(name)
+    out, din, dparam = ref_grads(g, torch.float32)
+    assert out.shape == g.out.shape
+    assert set(dparam) == set(g.dparam) and set(g.dparam) <= set(g.sd)
+    errs = {"out": rel_l2(out, g.out)}
+    errs.update({"d" + k: rel_l2(v, g.din[k]) for k, v in din.items()})
+    errs.update({"dW:" + k: v for k, v in grad_errors(dparam, g.dparam, g.sd).items()})
+    assert errs["out"] < REF_TOL, errs["out"]
+    bad = {k: v for k, v in errs.items() if k != "out" and not v < 5 * REF_TOL}
+    assert not bad, bad
+
+
+def test_restatement_returns_the_recorded_weights():
+    g = wide_golden("enc_softmax_w68_weights")
+    attn = torch.from_numpy(np.load(os.path.join(GOLDEN, SUB + "enc_softmax_w68_weights.npz"))["attn"])
+    _, w = run_ref(g, g.sd, g.inputs, return_attn=True)
+    assert w.shape == attn.shape == (2, 2, 65, 65)
+    assert rel_l2(w, attn) < REF_TOL
+    assert torch.allclose(attn.sum(-1), torch.ones(2, 2, 65), atol=1e-5)
+
+
+@pytest.mark.parametrize("name", WIDE_GOLDEN)
+def test_restatement_fp64_envelope(name):
+    """float32 restatement vs the float64 one: the numerical envelope the HIP path is judged in (the figures the GPU test's
+    docstring quotes come from here).  The figures are reported; the only bound is the sanity ceiling of
+    test_softmax_attention_cpu.py::test_restatement_fp64_envelope, 1e3 x the float32 epsilon, on every tensor, the output
+    included: the narrow file's extra 1e-6 on the output is not claimed here (the two-layer ex1 model, whose output is a
+    96-wide sum of size 0.09 behind a spectral regressor, measures 1.09e-6)."""
+    g = wide_golden(name)
+    o32, di32, dp32 = ref_grads(g, torch.float32)
+    o64, di64, dp64 = ref_grads(g, torch.float64)
+    errs = {"out": rel_l2(o32, o64)}
+    errs.update({"d" + k: rel_l2(v, di64[k]) for k, v in di32.items()})
+    errs.update({"dW:" + k: v for k, v in grad_errors(dp32, dp64, g.sd).items()})
+    worst = max(errs, key=errs.get)
+    over = {k: f"{v:.1e}" for k, v in errs.items() if v > 2e-6}
+    print(f"{name}: out {errs['out']:.2e}, worst {worst} {errs[worst]:.2e}, above 2e-6: {over}")
+    assert errs[worst] < 6e-5, (worst, errs[worst])
+
+
+def test_fixtures_are_the_wide_shapes_and_hold_arrays_only():
+    files = sorted(f[:-4] for f in os.listdir(os.path.join(GOLDEN, SUB)) if f.endswith(".npz"))
+    assert files == sorted(WIDE_GOLDEN + WIDE_PARTS)
+    for f in files:
+        path = os.path.join(GOLDEN, SUB, f + ".npz")
+        assert os.path.getsize(path) < (1 << 20), f
+        z = np.load(path, allow_pickle=False)
+        for k in z.files:
+            assert k in ("meta", "out", "cot", "attn") or k.split("/")[0] in ("sd", "in", "din", "dparam", "mask"), (f, k)
+            assert z[k].dtype.kind in "fiub", (f, k, z[k].dtype)
+    widths = {}
+    for name in WIDE_GOLDEN:
+        m = wide_golden(name).meta
+        c = m if m["kind"] == "encoder_layer" else m["config"]
+        assert c["attention_type"] == "softmax"
+        d = c["d_model"] if m["kind"] == "encoder_layer" else c["n_hidden"]
+        widths[name] = 4 * ((d // c["n_head"] + c["pos_dim"] + 3) // 4)
+    assert widths == {"enc_softmax_w100": 100, "enc_softmax_w100_replay": 100, "enc_softmax_w68": 68,
+                      "enc_softmax_w68_replay": 68, "enc_softmax_w68_weights": 68, "model_burgers_softmax_ex1": 100}
+
+
+def test_model_fixture_is_the_shipped_ex1_configuration():
+    """Everything but the attention type and the number of layers (2 of 4: the size limit of a committed file)."""
+    import yaml
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "galerkin-transformer_amd", "config.yml")) as f:
+        ex1 = yaml.full_load(f)["ex1_burgers"]
+    cfg = wide_golden("model_burgers_softmax_ex1").meta["config"]
+    assert dict(ex1, attention_type="softmax", num_encoder_layers=2) == cfg
+    assert json.loads(json.dumps(ex1))["attention_type"] == "fourier" and ex1["num_encoder_layers"] == 4
+
+
+def test_wide_symbols_declared_bound_and_exported():
+    from galerkin_transformer import _hip
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hdr = open(os.path.join(root, "include", "gt_hip.h")).read()
+    lib = ctypes.CDLL(_hip.lib_path())
+    for s in WIDE_SYMBOLS:
+        assert s + "(" in hdr, s
+        assert s in _hip.EXPORTED_SYMBOLS, s
+        assert hasattr(lib, s), s
+        narrow = s.replace("_wide", "")
+        assert _hip._PROTOS[s] == _hip._PROTOS[narrow], s          # same signature as the narrow entry point
+    assert _hip.lib().gt_abi_version() == 21 and _hip.ABI_VERSION == 21        # symbols are only added
+    assert _hip.SOFTMAX_DP == (20, 36, 52)
+    assert _hip.SOFTMAX_DP_WIDE == (68, 100)
+
+
+def test_entry_point_follows_the_width():
+    from galerkin_transformer import _hip
+    for DP in _hip.SOFTMAX_DP + (16, 44, 84, 116):          # unsupported widths go to the narrow symbol: GT_ENOTSUP there
+        assert _hip._softmax_sym(DP, "fwd") == "gt_softmax_attn_fwd"
+    for DP in _hip.SOFTMAX_DP_WIDE:
+        assert [_hip._softmax_sym(DP, t) for t in ("fwd", "bwd_q", "bwd_kv")] == list(WIDE_SYMBOLS)
+
+
+@pytest.mark.parametrize("d_model,n_head,pos_dim", ((96, 1, 1), (128, 2, 2)))
+def test_cpu_call_reaches_the_operator(d_model, n_head, pos_dim):
+    """The wide layers pass every Python-side gate (module, operator wrapper) and stop at the HIP operator's device check."""
+    import galerkin_transformer as gt
+    layer = gt.SimpleTransformerEncoderLayer(d_model=d_model, n_head=n_head, pos_dim=pos_dim, attention_type="softmax",
+                                             layer_norm=False)
+    with pytest.raises(RuntimeError, match="no CPU fallback") as e:
+        layer(torch.randn(1, 8, d_model), torch.rand(1, 8, pos_dim))
+    assert not isinstance(e.value, NotImplementedError)
+
+
+def test_gate_lists_both_sets_and_still_refuses_44():
+    """The operator's width gate.  A call without a device stops at the device check in front of it, so here the gate is
+    read off the operator's source; test_softmax_wide_gpu.py calls it (DP = 44 raises before any launch)."""
+    import inspect
+    from galerkin_transformer import _hip, ops
+    src = inspect.getsource(ops.SimpleAttentionFn.forward)
+    assert "DP not in H.SOFTMAX_DP + H.SOFTMAX_DP_WIDE" in src and "no kernel" in src
+    assert 44 not in _hip.SOFTMAX_DP + _hip.SOFTMAX_DP_WIDE

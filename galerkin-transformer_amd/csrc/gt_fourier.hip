@@ -34,6 +34,7 @@ struct FourierP {
 
 constexpr int FA_TS = 64;        // stream rows per LDS tile
 constexpr int FA_OW = 32;        // owner rows per wave
+constexpr int FA_WIDE_KS = 17;   // DP >= 68: the wide instances (gt_fourier_attn_wide)
 enum { FA_PLAIN = 0, FA_DROP = 1, FA_MASK = 2 };
 
 __device__ __attribute__((aligned(16))) float fa_zero16[4] = {0.f, 0.f, 0.f, 0.f};
@@ -52,8 +53,12 @@ typedef const __attribute__((address_space(1))) void* fa_glb_ptr_t;
 // Dropout (MODE == FA_DROP): the mask of score element idx is fmix32(idx*G + key) >= thresh (gt_common.h);
 // idx is affine in the stream row, so idx*G + key is carried by additions; the owner fragments are pre-scaled
 // by scale/(1-p) and a dropped score is a select, not a multiply.
+//
+// Blocks per CU: the wide instances (DP = 68 / 100) stage 68 / 100 KiB of stream tiles per block: at most two blocks fit a
+// CU at DP = 68, one at DP = 100, so they are bounded at one and the allocator is free to use AGPRs (gt_softmax.hip).  The
+// bounds of DP = 20 / 36 / 52 are what they were.
 template <int KS, bool DUAL, int MODE>     // KS = DP/4 contraction steps of the first product
-__global__ __launch_bounds__(256, DUAL ? (KS > 9 ? 1 : 2) : (KS > 9 ? 2 : 3)) void fourier_core_kernel(const FourierP p) {
+__global__ __launch_bounds__(256, KS >= FA_WIDE_KS ? 1 : DUAL ? (KS > 9 ? 1 : 2) : (KS > 9 ? 2 : 3)) void fourier_core_kernel(const FourierP p) {
     constexpr int DP = 4 * KS, NF = (DP - 4) / 16, XC = DP - 4, TILE = FA_TS * DP;
     static_assert(DP % 16 == 4, "head tile width must be 16*NF + 4");
     __shared__ __attribute__((aligned(16))) float smem[2][2][TILE];
@@ -66,6 +71,9 @@ __global__ __launch_bounds__(256, DUAL ? (KS > 9 ? 1 : 2) : (KS > 9 ? 2 : 3)) vo
     const uint32_t zn = ((uint32_t)b * (uint32_t)p.h + (uint32_t)head) * (uint32_t)p.n;
     const int ntile = (p.n + FA_TS - 1) / FA_TS;
 
+    // The tile image is 64*DP floats = KS chunks of 256 floats (64 lanes x one float4), chunk q = wave + 4i taken by wave
+    // `wave` in its round i: the guard q < KS ends the last round early (KS = 17: q = 16 only; KS = 25: q = 24 only), and
+    // chunk KS - 1 ends at float 256*KS = 64*DP, the end of smem[buf][*] exactly -- at any KS, the wide ones included.
     auto issue = [&](int t, int buf) {
         const int s0 = t * FA_TS;
 #pragma unroll
@@ -276,9 +284,11 @@ static void fourier_launch(const FourierP& p, bool dual, dim3 grid, hipStream_t 
 
 using namespace gt;
 
-extern "C" int gt_fourier_attn(const float* F1, const float* F2, const float* T1, const float* T2, float* O1,
-                               float* O2, int32_t B, int32_t n, int32_t h, int32_t DP, float scale,
-                               const float* mask, const gt_dropout* drop, int32_t owner_is_key, void* stream) {
+// WIDE selects the instance set of the entry point: DP in {20, 36, 52} (gt_fourier_attn) or {68, 100} (gt_fourier_attn_wide).
+template <bool WIDE>
+static int fourier_attn(const float* F1, const float* F2, const float* T1, const float* T2, float* O1, float* O2, int32_t B,
+                        int32_t n, int32_t h, int32_t DP, float scale, const float* mask, const gt_dropout* drop,
+                        int32_t owner_is_key, void* stream) {
     if (!F1 || !T1 || !T2 || !O1 || B <= 0 || n <= 0 || h <= 0 || DP <= 0) return GT_EINVAL;
     const bool dual = F2 != nullptr;
     if (dual && !O2) return GT_EINVAL;
@@ -290,12 +300,33 @@ extern "C" int gt_fourier_attn(const float* F1, const float* F2, const float* T1
     FourierP p{F1, F2, T1, T2, O1, O2, mask, make_drop(mask ? nullptr : drop), n, h, scale, owner_is_key};
     dim3 grid((unsigned)ceil_div(n, 4 * FA_OW), (unsigned)h, (unsigned)B);
     hipStream_t st = (hipStream_t)stream;
-    switch (DP) {
-        case 20: fourier_launch<5>(p, dual, grid, st); break;
-        case 36: fourier_launch<9>(p, dual, grid, st); break;
-        case 52: fourier_launch<13>(p, dual, grid, st); break;
-        default: return GT_ENOTSUP;
+    if (WIDE) {
+        switch (DP) {
+            case 68: fourier_launch<17>(p, dual, grid, st); break;
+            case 100: fourier_launch<25>(p, dual, grid, st); break;
+            default: return GT_ENOTSUP;
+        }
+    } else {
+        switch (DP) {
+            case 20: fourier_launch<5>(p, dual, grid, st); break;
+            case 36: fourier_launch<9>(p, dual, grid, st); break;
+            case 52: fourier_launch<13>(p, dual, grid, st); break;
+            default: return GT_ENOTSUP;
+        }
     }
     GT_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int gt_fourier_attn(const float* F1, const float* F2, const float* T1, const float* T2, float* O1,
+                               float* O2, int32_t B, int32_t n, int32_t h, int32_t DP, float scale,
+                               const float* mask, const gt_dropout* drop, int32_t owner_is_key, void* stream) {
+    return fourier_attn<false>(F1, F2, T1, T2, O1, O2, B, n, h, DP, scale, mask, drop, owner_is_key, stream);
+}
+
+// The same pass at DP = 68 / 100: an entry point of its own, so that the narrow one keeps answering GT_ENOTSUP there.
+extern "C" int gt_fourier_attn_wide(const float* F1, const float* F2, const float* T1, const float* T2, float* O1,
+                                    float* O2, int32_t B, int32_t n, int32_t h, int32_t DP, float scale,
+                                    const float* mask, const gt_dropout* drop, int32_t owner_is_key, void* stream) {
+    return fourier_attn<true>(F1, F2, T1, T2, O1, O2, B, n, h, DP, scale, mask, drop, owner_is_key, stream);
 }

@@ -116,6 +116,8 @@ _PROTOS = {
     "gt_token_norm_bwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 5 + [C.c_void_p, C.c_int64, C.c_void_p]),
     "gt_fourier_attn": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.POINTER(GtDropout),
                                                                 C.c_int32, C.c_void_p]),
+    "gt_fourier_attn_wide": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.POINTER(GtDropout),
+                                                                     C.c_int32, C.c_void_p]),
     "gt_fourier16_image_bytes": (C.c_int64, [C.c_int32] * 4),
     "gt_fourier16_presplit": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 4 + [C.c_void_p]),
     "gt_fourier16_attn": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.POINTER(GtDropout),
@@ -1357,6 +1359,7 @@ def dft_synthesis(F, Z, Y, nb: int, n: int, P: int, Co: int, X2, W2, C2: int, bi
 
 
 FOURIER_DP = (20, 36, 52)
+FOURIER_DP_WIDE = (68, 100)   # d_k = 64 / 96: the same fp32-MFMA kernel behind an entry point of its own (gt_fourier_attn_wide)
 # head-tile widths of the two-term fp16 Fourier kernels (gt_fourier16.hip): those of the fp32-MFMA kernel and the wide ones
 # (d_k = 64 / 96 with coordinates).  FOURIER_DP itself also keys gt_fourier_attn, gt_galerkin_dkv and gt_galerkin_dkv_ln.
 FOURIER16_DP = FOURIER_DP + (68, 100)
@@ -1424,10 +1427,16 @@ def fourier16_attn(F1, F2, T1, T2, B: int, n: int, h: int, DP: int, scale: float
     return (O1, O2) if F2 is not None else O1
 
 
+def _fourier_sym(DP: int) -> str:
+    """Entry point of the fused fp32 Fourier pass for a head tile DP wide (an unsupported DP goes to the narrow one, which
+    answers GT_ENOTSUP)."""
+    return "gt_fourier_attn_wide" if DP in FOURIER_DP_WIDE else "gt_fourier_attn"
+
+
 def fourier_attn(F1, F2, T1, T2, B: int, n: int, h: int, DP: int, scale: float, mask, drop, owner_is_key: bool,
                  O1=None, O2=None):
-    """One pass of gt_fourier_attn on head tiles [B*n, h, DP]; returns O1 (and O2 when F2 is given).  O1 / O2 may
-    be preallocated dense [B*n, h, DP] tensors (e.g. slices of the head-tile gradient buffer)."""
+    """One pass of gt_fourier_attn (DP 68 / 100: gt_fourier_attn_wide) on head tiles [B*n, h, DP]; returns O1 (and O2 when
+    F2 is given).  O1 / O2 may be preallocated dense [B*n, h, DP] tensors (e.g. slices of the head-tile gradient buffer)."""
     need_f32_cuda(F1, F2, T1, T2, mask, O1, O2)
     if O1 is None:
         O1 = torch.empty(B * n, h, DP, dtype=torch.float32, device=F1.device)
@@ -1435,10 +1444,11 @@ def fourier_attn(F1, F2, T1, T2, B: int, n: int, h: int, DP: int, scale: float, 
         O2 = torch.empty_like(O1)
     dp = C.byref(drop) if (drop is not None and drop.p > 0) else None
     nprod = 2 if F2 is not None else 1
-    check(_timed("gt_fourier_attn", 4.0 * nprod * B * h * n * n * DP, 4.0 * (3 + nprod) * B * n * h * DP,
-                 lambda: lib().gt_fourier_attn(F1.data_ptr(), ptr(F2), T1.data_ptr(), T2.data_ptr(), O1.data_ptr(),
-                                               ptr(O2), B, n, h, DP, scale, ptr(mask), dp, int(owner_is_key),
-                                               stream_ptr()), shape=(B, n, h, DP, nprod)), "gt_fourier_attn")
+    sym = _fourier_sym(DP)
+    check(_timed(sym, 4.0 * nprod * B * h * n * n * DP, 4.0 * (3 + nprod) * B * n * h * DP,
+                 lambda: getattr(lib(), sym)(F1.data_ptr(), ptr(F2), T1.data_ptr(), T2.data_ptr(), O1.data_ptr(),
+                                             ptr(O2), B, n, h, DP, scale, ptr(mask), dp, int(owner_is_key),
+                                             stream_ptr()), shape=(B, n, h, DP, nprod)), sym)
     return (O1, O2) if F2 is not None else O1
 
 

@@ -340,6 +340,9 @@ class SimpleAttention(nn.Module):
     'softmax' (scaled dot-product attention, the dropout mask on the softmax output; fp32 arithmetic in every precision
     mode) needs coordinates: head tiles of width round4(d_k + pos_dim) in {20, 36, 52, 68, 100}, i.e. d_k in (16, 32, 48, 64,
     96) with pos_dim >= 1 (the shipped ex1 configuration, d_model 96 / one head, is the 100-wide one); the coordinate-free call (``pos is None`` or ``pos_dim == 0``) raises NotImplementedError.
+    'fourier' with ``need_weights=False`` is fused (no n x n matrix in HBM) at the same five head-tile widths in every
+    precision mode: the two-term fp16 kernel in the default arithmetic, the fp32-MFMA kernel (gt_fourier_attn, and
+    gt_fourier_attn_wide at 68 / 100) under ``set_precision('f32')`` and the bf16 modes; other widths materialise.
     Other variants of the reference are baselines outside the hot path."""
 
     def __init__(self, n_head, d_model, pos_dim: int = 1, attention_type="fourier", dropout=0.1,

@@ -1260,8 +1260,9 @@ def _fourier_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn, d_out, dims, sign, 
     wpad = torch.zeros(d, h, DP, dtype=torch.float32, device=dev)
     wpad[:, :, :Dr] = wf.reshape(d, h, Dr)
     wpad = wpad.reshape(d, hD)
-    # (the wide head tiles, d_k = 64 / 96, have instances of the fp16 kernel only: in the f32 / bf16 modes they materialise)
-    flash = (not need_w) and (DP in H.FOURIER_DP or (DP in H.FOURIER16_DP and H.fourier16_active()))
+    # fp16 arithmetic active: every width of the fp16 kernel runs on it; otherwise (f32 / bf16 modes) the fp32-MFMA kernel,
+    # which has the same widths behind two entry points (H.fourier_attn picks)
+    flash = (not need_w) and (DP in H.FOURIER_DP + H.FOURIER_DP_WIDE or (DP in H.FOURIER16_DP and H.fourier16_active()))
     f16 = flash and H.fourier16_active()
     # fp16 arithmetic: the p = 0.5 score mask is drawn per 4 x 4 block (one hash per block: gt_hip.h), by the fused
     # kernels and by the materialising path alike

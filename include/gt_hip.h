@@ -444,11 +444,16 @@ int gt_token_norm_bwd(const float* X, const float* dY, const float* gamma, const
  *     forward        F1 = Q',  F2 = NULL, T1 = K', T2 = V',  owner_is_key = 0  ->  O1 = out
  *     d/dQ'          F1 = dO,  F2 = NULL, T1 = V', T2 = K',  owner_is_key = 0  ->  O1 = dQ'
  *     d/dV', d/dK'   F1 = K',  F2 = V',   T1 = Q', T2 = dO,  owner_is_key = 1  ->  O1 = dV', O2 = dK'
- * DP in {20, 36, 52} (else GT_ENOTSUP: materialise through gt_gemm).
+ * gt_fourier_attn: DP in {20, 36, 52}, else GT_ENOTSUP.  gt_fourier_attn_wide: the same pass, arguments and contracts for
+ * the 64- and 96-wide heads, DP in {68, 100}, else GT_ENOTSUP (additive, same ABI; each entry point refuses the other's
+ * widths).  A width neither takes has no fused fp32 kernel: materialise through gt_gemm.
  * ------------------------------------------------------------------------------------------- */
 int gt_fourier_attn(const float* F1, const float* F2, const float* T1, const float* T2, float* O1, float* O2,
                     int32_t B, int32_t n, int32_t h, int32_t DP, float scale, const float* mask,
                     const gt_dropout* drop, int32_t owner_is_key, void* stream);
+int gt_fourier_attn_wide(const float* F1, const float* F2, const float* T1, const float* T2, float* O1, float* O2,
+                         int32_t B, int32_t n, int32_t h, int32_t DP, float scale, const float* mask,
+                         const gt_dropout* drop, int32_t owner_is_key, void* stream);
 
 /* The same operator (layers.py:672-705, the three uses above) in the two-term fp16 arithmetic (GT_PREC_F16X2: three products
  * per contraction on v_mfma_f32_16x16x32_f16, fp32 accumulation, fp32-class results) -- ABI v19.  The head tiles are split

@@ -317,6 +317,38 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+_PLAIN = frozenset((int, float, bool, type(None)))
+
+
+def _carg(a):
+    """One argument of a C-ABI call: a tensor becomes its device pointer and a GtDropout goes by reference unless its p is 0
+    (the entry points take NULL for "no dropout"); numbers, None, an explicit C.byref and raw pointers pass unchanged."""
+    t = type(a)
+    if t in _PLAIN:
+        return a
+    if t is GtDropout:
+        return C.byref(a) if (a.p > 0) else None
+    return a.data_ptr() if isinstance(a, torch.Tensor) else a
+
+
+def _launch(sym, *args, key=None, flops=0.0, nbytes=0.0, shape=None, ws=None):
+    """Launch the entry point `sym` on torch's current stream: `args` are its arguments without the stream (converted by
+    _carg), `ws` a scratch tensor appended as (pointer, bytes), and the stream goes last.  `key` (default: the symbol) names the
+    launch in a Profile and in the error raised for a non-zero return; flops / nbytes / shape go to the Profile record.
+    By hand instead: gemm, ffn_fwd and ffn_bwd (the hottest host paths, which also record a replay) and the two launches
+    that are no Profile record, advance_seed and debug_conv0_mask."""
+    key = key or sym
+    fn = getattr(lib(), sym)
+    a = [_carg(x) for x in args]
+    if ws is not None:
+        a += (ws.data_ptr(), ws.numel())
+    if _prof is None and not _DEBUG_SYNC:
+        rc = fn(*a, stream_ptr())
+    else:
+        rc = _timed(key, flops, nbytes, lambda: fn(*a, stream_ptr()), shape=shape)
+    check(rc, key)
+
+
 def need_f32_cuda(*ts: torch.Tensor):
     for t in ts:
         if t is None:
@@ -514,7 +546,7 @@ def advance_seed(device: Optional[torch.device] = None, inc: int = 1):
     """Bump the dropout seed (captured into graphs: every replay draws fresh masks)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     s = seed_state(device)
-    check(lib().gt_seed_advance(s.data_ptr(), inc, stream_ptr()), "gt_seed_advance")
+    check(lib().gt_seed_advance(s.data_ptr(), inc, stream_ptr()), "gt_seed_advance")       # (not a Profile record)
 
 
 def dropout_desc(p: float, salt: int, device: torch.device) -> GtDropout:
@@ -581,12 +613,11 @@ class _WeightPacks:
             chunk = items[i0:i0 + 64]
             descs = (GtGemmDesc * len(chunk))(*[e[0] for _, e in chunk])
             outs = (C.c_void_p * len(chunk))(*[e[1].data_ptr() for _, e in chunk])
-            rc = _timed("gt_gemm_pack_b_many", 0.0, 0.0,
-                        lambda: lib().gt_gemm_pack_b_many(descs, outs, len(chunk), stream_ptr()), shape=(len(chunk),))
-            if rc == -4:               # GT_ENOTSUP (an entry no longer takes the packed path): per-call packs this bracket
+            try:
+                _launch("gt_gemm_pack_b_many", descs, outs, len(chunk), shape=(len(chunk),))
+            except GtNotSupported:     # (an entry no longer takes the packed path): per-call packs this bracket
                 self.ready = set()
                 return
-            check(rc, "gt_gemm_pack_b_many")
             self.ready.update(k for k, _ in chunk)
 
     def invalidate(self):
@@ -603,6 +634,12 @@ weight_packs = _WeightPacks()
 
 
 # ----------------------------------------------------------------------------------- GEMM
+def _new_desc() -> GtGemmDesc:
+    d = GtGemmDesc()
+    lib().gt_gemm_desc_init(C.byref(d))
+    return d
+
+
 def gemm(A: torch.Tensor, B: torch.Tensor, Cout: torch.Tensor, M: int, N: int, K: int, *,
          layout_a: int = 0, layout_b: int = 0, lda: int, ldb: int, ldc: int,
          batch: Tuple[int, int] = (1, 1), a_bs=(0, 0), b_bs=(0, 0), c_bs=(0, 0), split_k: int = 1,
@@ -631,8 +668,7 @@ def gemm(A: torch.Tensor, B: torch.Tensor, Cout: torch.Tensor, M: int, N: int, K
     weight gradient.  Cout may be None for a GT_EP_HEADNORM launch that stores no raw projection (hn["skip_raw"] == 7)."""
     need_f32_cuda(A, B, Cout, bias, rp_a, rp_b, add, pre, aux, res, a_colsum)
     L = lib()
-    d = GtGemmDesc()
-    L.gt_gemm_desc_init(C.byref(d))
+    d = _new_desc()
     d.M, d.N, d.K = M, N, K
     d.layout_a, d.layout_b = layout_a, layout_b
     d.batch0, d.batch1 = batch
@@ -734,11 +770,9 @@ def ffn_fwd_supported(T: int, d: int, f: int, act: int) -> bool:
 def _ffn_packs(T, specs, dev_tensor):
     """b_packed of the two products of a fused FeedForward launch when the once-per-step pack holds them, else (None, None).
     specs: ((weight, layout_b, ldb, N, K), ...) -- the descriptors H.gemm would build for them."""
-    L = lib()
     packs = []
     for (Bw, lb, ldb, N, K) in specs:
-        dsc = GtGemmDesc()
-        L.gt_gemm_desc_init(C.byref(dsc))
+        dsc = _new_desc()
         dsc.M, dsc.N, dsc.K, dsc.lda, dsc.ldb, dsc.ldc, dsc.layout_b = T, N, K, K, ldb, N, lb
         dsc.A, dsc.B, dsc.C = dev_tensor.data_ptr(), Bw.data_ptr(), dev_tensor.data_ptr()
         dsc.precision = PREC_F16X2
@@ -762,8 +796,7 @@ def ffn_fwd(x2: torch.Tensor, w1: torch.Tensor, b1, w2: torch.Tensor, b2, res, d
         ws = workspace(x2.device, L.gt_ffn_fwd_ws_bytes(T, d, f))
         wsp, wsn = ws.data_ptr(), ws.numel()
     bits = torch.empty(L.gt_ffn_bits_bytes(T), dtype=torch.uint8, device=x2.device) if want_bits else None
-    dh = C.byref(drop_h) if (drop_h is not None and drop_h.p > 0) else None
-    do = C.byref(drop_o) if (drop_o is not None and drop_o.p > 0) else None
+    dh, do = _carg(drop_h), _carg(drop_o)
     st = stream_ptr()
     call = lambda: L.gt_ffn_fwd(x2.data_ptr(), T, d, f, w1.data_ptr(), ptr(b1), w2.data_ptr(), ptr(b2), ptr(res), dh, do, act,
                                 hid.data_ptr(), out.data_ptr(), ptr(bits), p1, p2, wsp, wsn, st)
@@ -787,7 +820,7 @@ def ffn_bwd(gm: torch.Tensor, w2: torch.Tensor, w1: torch.Tensor, bits: torch.Te
     if p2 is None:
         ws = workspace(gm.device, L.gt_ffn_fwd_ws_bytes(T, d, f))
         wsp, wsn = ws.data_ptr(), ws.numel()
-    m2 = C.byref(mask2) if (mask2 is not None and mask2.p > 0) else None
+    m2 = _carg(mask2)
     st = stream_ptr()
     call = lambda: L.gt_ffn_bwd(gm.data_ptr(), T, d, f, w2.data_ptr(), w1.data_ptr(), bits.data_ptr(), float(hid_scale), ptr(res),
                                 gh.data_ptr(), dx.data_ptr(), ptr(dx_masked), m2, p2, p1, wsp, wsn, st)
@@ -798,8 +831,7 @@ def ffn_bwd(gm: torch.Tensor, w2: torch.Tensor, w1: torch.Tensor, bits: torch.Te
 
 def gemm_kernel_name(A, B, M, N, K, *, layout_a=0, layout_b=0, lda, ldb, ldc, split_k=1, precision=None) -> str:
     """Symbol of the kernel gt_gemm launches for a plain (epilogue-free, unbatched) product."""
-    d = GtGemmDesc()
-    lib().gt_gemm_desc_init(C.byref(d))
+    d = _new_desc()
     d.M, d.N, d.K, d.layout_a, d.layout_b, d.split_k = M, N, K, layout_a, layout_b, split_k
     d.precision = _precision[0] if precision is None else PREC_CODE[precision]
     d.A, d.lda, d.B, d.ldb, d.ldc = A.data_ptr(), lda, B.data_ptr(), ldb, ldc
@@ -809,8 +841,7 @@ def gemm_kernel_name(A, B, M, N, K, *, layout_a=0, layout_b=0, lda, ldb, ldc, sp
 
 
 def gemm_plan(M, N, K, batch=(1, 1), split_k=1):
-    d = GtGemmDesc()
-    lib().gt_gemm_desc_init(C.byref(d))
+    d = _new_desc()
     d.M, d.N, d.K = M, N, K
     d.batch0, d.batch1 = batch
     d.split_k = split_k
@@ -825,16 +856,14 @@ def colsum(A: torch.Tensor, M: int, N: int, lda: int, a_drop: Optional[GtDropout
     need_f32_cuda(A)
     out = torch.empty(N, dtype=torch.float32, device=A.device)
     ws = workspace(A.device, 1024 * max(N, 64) * 4)       # >= the bounded number of partial rows
-    dp = C.byref(a_drop) if (a_drop is not None and a_drop.p > 0) else None
-    check(_timed("gt_colsum", 0, 0, lambda: lib().gt_colsum(A.data_ptr(), lda, M, N, dp, sign, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                          stream_ptr())), "gt_colsum")
+    _launch("gt_colsum", A, lda, M, N, a_drop, sign, out, ws=ws)
     return out
 
 
 def slab_reduce(slabs: torch.Tensor, n_slabs: int, stride: int, n: int, out: torch.Tensor,
                 alpha: float = 1.0):
     need_f32_cuda(slabs, out)
-    check(_timed("gt_slab_reduce", 0, 0, lambda: lib().gt_slab_reduce(slabs.data_ptr(), stride, n_slabs, n, alpha, out.data_ptr(), stream_ptr())), "gt_slab_reduce")
+    _launch("gt_slab_reduce", slabs, stride, n_slabs, n, alpha, out)
     return out
 
 
@@ -842,19 +871,15 @@ def act_bwd(dout: torch.Tensor, pre: torch.Tensor, act: int) -> torch.Tensor:
     need_f32_cuda(dout, pre)
     dout = dout.contiguous()
     out = torch.empty_like(pre)
-    check(_timed("gt_act_bwd", 0, 0, lambda: lib().gt_act_bwd(dout.data_ptr(), pre.data_ptr(), out.data_ptr(), pre.numel(), act, stream_ptr())), "gt_act_bwd")
+    _launch("gt_act_bwd", dout, pre, out, pre.numel(), act)
     return out
 
 
 def dropout_apply(x: torch.Tensor, d: GtDropout) -> torch.Tensor:
     need_f32_cuda(x)
     out = torch.empty_like(x)
-    check(_timed("gt_dropout_apply", 0, 0, lambda: lib().gt_dropout_apply(x.data_ptr(), out.data_ptr(), x.numel(), C.byref(d), stream_ptr())), "gt_dropout_apply")
+    _launch("gt_dropout_apply", x, out, x.numel(), C.byref(d))      # (by reference whatever its p)
     return out
-
-
-def _dref(d):
-    return C.byref(d) if (d is not None and d.p > 0) else None
 
 
 def dropact_fwd(x: torch.Tensor, d1, act1: int, d2, act2: int) -> torch.Tensor:
@@ -862,9 +887,7 @@ def dropact_fwd(x: torch.Tensor, d1, act1: int, d2, act2: int) -> torch.Tensor:
     need_f32_cuda(x)
     y = torch.empty_like(x)
     n = x.numel()
-    check(_timed("gt_dropact_fwd", 0, 8.0 * n, lambda: lib().gt_dropact_fwd(x.data_ptr(), y.data_ptr(), n, _dref(d1), act1,
-                                                                         _dref(d2), act2, stream_ptr()), shape=(n,)),
-          "gt_dropact_fwd")
+    _launch("gt_dropact_fwd", x, y, n, d1, act1, d2, act2, nbytes=8.0 * n, shape=(n,))
     return y
 
 
@@ -872,9 +895,7 @@ def dropact_bwd(x: torch.Tensor, gy: torch.Tensor, d1, act1: int, d2, act2: int)
     need_f32_cuda(x, gy)
     gx = torch.empty_like(x)
     n = x.numel()
-    check(_timed("gt_dropact_bwd", 0, 12.0 * n, lambda: lib().gt_dropact_bwd(x.data_ptr(), gy.data_ptr(), gx.data_ptr(), n,
-                                                                          _dref(d1), act1, _dref(d2), act2, stream_ptr()),
-                 shape=(n,)), "gt_dropact_bwd")
+    _launch("gt_dropact_bwd", x, gy, gx, n, d1, act1, d2, act2, nbytes=12.0 * n, shape=(n,))
     return gx
 
 
@@ -889,8 +910,7 @@ def headnorm_fwd(qkv: torch.Tensor, pos: Optional[torch.Tensor], gamma: Optional
     DP = round4(dk + p)
     out = torch.empty(3, T, h, DP, dtype=torch.float32, device=qkv.device)
     stats = torch.empty(2, T, h, 2, dtype=torch.float32, device=qkv.device)
-    check(_timed("gt_headnorm_fwd", 0, 0, lambda: lib().gt_headnorm_fwd(qkv.data_ptr(), ptr(pos), ptr(gamma), ptr(beta), T, h, dk, p, norm_mask,
-                                eps, out.data_ptr(), stats.data_ptr(), stream_ptr())), "gt_headnorm_fwd")
+    _launch("gt_headnorm_fwd", qkv, pos, gamma, beta, T, h, dk, p, norm_mask, eps, out, stats)
     return out, stats
 
 
@@ -901,11 +921,8 @@ def headnorm_bwd(d_out: torch.Tensor, qkv: torch.Tensor, gamma: Optional[torch.T
     d_qkv = torch.empty(T, 3 * h * dk, dtype=torch.float32, device=dev)
     dgamma = torch.empty(2, h, dk, dtype=torch.float32, device=dev)
     dbeta = torch.empty(2, h, dk, dtype=torch.float32, device=dev)
-    need = lib().gt_headnorm_bwd_ws_bytes(T, h, dk)
-    ws = workspace(dev, need)
-    check(_timed("gt_headnorm_bwd", 0, 0, lambda: lib().gt_headnorm_bwd(d_out.data_ptr(), qkv.data_ptr(), ptr(gamma), stats.data_ptr(), T, h, dk, p,
-                                norm_mask, d_qkv.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                ws.data_ptr(), ws.numel(), stream_ptr())), "gt_headnorm_bwd")
+    ws = workspace(dev, lib().gt_headnorm_bwd_ws_bytes(T, h, dk))
+    _launch("gt_headnorm_bwd", d_out, qkv, gamma, stats, T, h, dk, p, norm_mask, d_qkv, dgamma, dbeta, ws=ws)
     return d_qkv, dgamma, dbeta
 
 
@@ -918,10 +935,8 @@ def galerkin_finalize_fwd(slabs: torch.Tensor, n_slabs: int, slab_stride: int, B
     Mt = torch.empty(B, h, DP, DP, dtype=torch.float32, device=dev)
     P = torch.empty(B, h * DP, d, dtype=torch.float32, device=dev)
     Pv = torch.empty(B, h * (Dr - value_rows_of), d, dtype=torch.float32, device=dev) if value_rows_of is not None else None
-    dp = C.byref(drop) if (drop is not None and drop.p > 0) else None
-    check(_timed("gt_galerkin_finalize_fwd", 0, 0, lambda: lib().gt_galerkin_finalize_fwd(slabs.data_ptr(), n_slabs, slab_stride, B, h, DP, Dr, d, n_tokens,
-                                         ptr(mask), dp, Wfc.data_ptr(), Mt.data_ptr(), P.data_ptr(), ptr(Pv),
-                                         value_rows_of or 0, stream_ptr())), "gt_galerkin_finalize_fwd")
+    _launch("gt_galerkin_finalize_fwd", slabs, n_slabs, slab_stride, B, h, DP, Dr, d, n_tokens, mask, drop, Wfc, Mt, P, Pv,
+            value_rows_of or 0)
     return (Mt, P) if value_rows_of is None else (Mt, P, Pv)
 
 
@@ -932,10 +947,7 @@ def galerkin_finalize_bwd(dPt: torch.Tensor, Mt: torch.Tensor, mask: Optional[to
     dev = dPt.device
     dM = torch.empty(B, h, DP, DP, dtype=torch.float32, device=dev)
     dW_slabs = torch.empty(B, d, h * Dr, dtype=torch.float32, device=dev)
-    dp = C.byref(drop) if (drop is not None and drop.p > 0) else None
-    check(_timed("gt_galerkin_finalize_bwd", 0, 0, lambda: lib().gt_galerkin_finalize_bwd(dPt.data_ptr(), Mt.data_ptr(), ptr(mask), dp, Wfc.data_ptr(), B, h,
-                                         DP, Dr, d, n_tokens, dM.data_ptr(), dW_slabs.data_ptr(),
-                                         stream_ptr())), "gt_galerkin_finalize_bwd")
+    _launch("gt_galerkin_finalize_bwd", dPt, Mt, mask, drop, Wfc, B, h, DP, Dr, d, n_tokens, dM, dW_slabs)
     return dM, dW_slabs
 
 
@@ -945,8 +957,7 @@ def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps:
     T = x.numel() // d
     y = torch.empty_like(x)
     stats = torch.empty(T, 2, dtype=torch.float32, device=x.device)
-    check(_timed("gt_layernorm_fwd", 0, 0, lambda: lib().gt_layernorm_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), T, d, eps, y.data_ptr(),
-                                 stats.data_ptr(), stream_ptr())), "gt_layernorm_fwd")
+    _launch("gt_layernorm_fwd", x, gamma, beta, T, d, eps, y, stats)
     return y, stats
 
 
@@ -958,9 +969,7 @@ def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, stats:
     dg = torch.empty(d, dtype=torch.float32, device=x.device)
     db = torch.empty(d, dtype=torch.float32, device=x.device)
     ws = workspace(x.device, lib().gt_layernorm_bwd_ws_bytes(T, d))
-    check(_timed("gt_layernorm_bwd", 0, 0, lambda: lib().gt_layernorm_bwd(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), stats.data_ptr(), T, d,
-                                 dx.data_ptr(), dg.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(),
-                                 stream_ptr())), "gt_layernorm_bwd")
+    _launch("gt_layernorm_bwd", dy, x, gamma, stats, T, d, dx, dg, db, ws=ws)
     return dx, dg, db
 
 
@@ -968,8 +977,7 @@ def modemix_fwd(X: torch.Tensor, W: torch.Tensor, Y: torch.Tensor, B: int, Q: in
                 q_total: int, q_off: int):
     """X [B,2,q_total,Cin], W [Cin,Cout,Q,2], Y [B,2,q_total,Cout] (written for q in [q_off,q_off+Q))."""
     need_f32_cuda(X, W, Y)
-    check(_timed("gt_modemix_fwd", 0, 0, lambda: lib().gt_modemix_fwd(X.data_ptr(), W.data_ptr(), B, Q, Cin, Cout, 2 * q_total * Cin,
-                               2 * q_total * Cout, q_total, q_total, q_off, Y.data_ptr(), stream_ptr())), "gt_modemix_fwd")
+    _launch("gt_modemix_fwd", X, W, B, Q, Cin, Cout, 2 * q_total * Cin, 2 * q_total * Cout, q_total, q_total, q_off, Y)
     return Y
 
 
@@ -978,9 +986,8 @@ def modemix_bwd(X: torch.Tensor, W: torch.Tensor, dY: torch.Tensor, dX: torch.Te
     need_f32_cuda(X, W, dY, dX, dW)
     need = lib().gt_modemix_bwd_ws_bytes(B, Q, Cin, Cout)
     ws = workspace(X.device, need) if need > 0 else None
-    check(_timed("gt_modemix_bwd", 0, 0, lambda: lib().gt_modemix_bwd(X.data_ptr(), W.data_ptr(), dY.data_ptr(), B, Q, Cin, Cout, 2 * q_total * Cin,
-                               2 * q_total * Cout, q_total, q_total, q_off, dX.data_ptr(), dW.data_ptr(),
-                               ptr(ws), ws.numel() if ws is not None else 0, stream_ptr())), "gt_modemix_bwd")
+    _launch("gt_modemix_bwd", X, W, dY, B, Q, Cin, Cout, 2 * q_total * Cin, 2 * q_total * Cout, q_total, q_total, q_off,
+            dX, dW, ws, ws.numel() if ws is not None else 0)      # (no scratch needed: NULL, 0)
     return dX, dW
 
 
@@ -1002,16 +1009,14 @@ def bilinear2d_fwd(x: torch.Tensor, size, in_nhwc: bool, out_nhwc: bool, act: in
     B, Cc, Hi, Wi = _shape4(x, in_nhwc)
     Ho, Wo = int(size[0]), int(size[1])
     y = torch.empty((B, Ho, Wo, Cc) if out_nhwc else (B, Cc, Ho, Wo), dtype=torch.float32, device=x.device)
-    nb = 4.0 * B * Cc * (Hi * Wi + Ho * Wo)
     aff = GtResizeAffine()
     aff.bias = ptr(bias)
     if rp_a is not None:
         aff.rp, aff.rp_a, aff.rp_lda = rp_a.shape[-1], rp_a.data_ptr(), rp_a.shape[-1]
         aff.rp_b, aff.rp_ldb = rp_b.data_ptr(), rp_ldb
-    check(_timed("gt_bilinear2d_fwd", 0, nb, lambda: lib().gt_bilinear2d_fwd_affine(
-        x.data_ptr(), y.data_ptr(), B, Cc, Hi, Wi, Ho, Wo, int(in_nhwc), int(out_nhwc), act, C.byref(aff),
-        stream_ptr()),
-        shape=(B, Cc, Hi, Ho, int(in_nhwc), int(out_nhwc))), "gt_bilinear2d_fwd")
+    _launch("gt_bilinear2d_fwd_affine", x, y, B, Cc, Hi, Wi, Ho, Wo, int(in_nhwc), int(out_nhwc), act, C.byref(aff),
+            key="gt_bilinear2d_fwd", nbytes=4.0 * B * Cc * (Hi * Wi + Ho * Wo),
+            shape=(B, Cc, Hi, Ho, int(in_nhwc), int(out_nhwc)))
     return y
 
 
@@ -1021,10 +1026,9 @@ def bilinear2d_bwd(g: torch.Tensor, y_saved: Optional[torch.Tensor], in_size, in
     B, Cc, Ho, Wo = _shape4(g, out_nhwc)
     Hi, Wi = int(in_size[0]), int(in_size[1])
     dx = torch.empty((B, Hi, Wi, Cc) if in_nhwc else (B, Cc, Hi, Wi), dtype=torch.float32, device=g.device)
-    nb = 4.0 * B * Cc * (Hi * Wi + Ho * Wo * (2 if y_saved is not None else 1))
-    check(_timed("gt_bilinear2d_bwd", 0, nb, lambda: lib().gt_bilinear2d_bwd(
-        g.data_ptr(), ptr(y_saved), dx.data_ptr(), B, Cc, Hi, Wi, Ho, Wo, int(in_nhwc), int(out_nhwc), act,
-        stream_ptr()), shape=(B, Cc, Hi, Ho, int(in_nhwc), int(out_nhwc))), "gt_bilinear2d_bwd")
+    _launch("gt_bilinear2d_bwd", g, y_saved, dx, B, Cc, Hi, Wi, Ho, Wo, int(in_nhwc), int(out_nhwc), act,
+            nbytes=4.0 * B * Cc * (Hi * Wi + Ho * Wo * (2 if y_saved is not None else 1)),
+            shape=(B, Cc, Hi, Ho, int(in_nhwc), int(out_nhwc)))
     return dx
 
 
@@ -1037,20 +1041,16 @@ def conv3x3_resize_fwd(x: torch.Tensor, w: torch.Tensor, size, drop: Optional[Gt
     B, Cin, Hh, Ww = x.shape
     Cout, Ho, Wo = w.shape[0], int(size[0]), int(size[1])
     y = torch.empty((B, Ho, Wo, Cout) if out_nhwc else (B, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
-    dp = C.byref(drop) if (drop is not None and drop.p > 0) else None
     bits = None
     if want_bits and out_nhwc and act == ACT_RELU:           # (the SiLU form re-evaluates in its backward: nothing to record)
         nb = lib().gt_conv3x3_resize_bits_bytes(B, Cout, Ho, Wo)
         if nb > 0:
             bits = torch.empty(nb, dtype=torch.uint8, device=x.device)
-    if out_nhwc:
-        call = lambda: lib().gt_conv3x3_resize_fwd_nhwc(x.data_ptr(), w.data_ptr(), y.data_ptr(), B, Cin, Cout, Hh, Ww, Ho,
-                                                        Wo, dp, act, ptr(bits), stream_ptr())
-    else:
-        call = lambda: lib().gt_conv3x3_resize_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), B, Cin, Cout, Hh, Ww, Ho, Wo,
-                                                   dp, act, stream_ptr())
-    check(_timed("gt_conv3x3_resize_fwd", 2.0 * 36 * Cin * y.numel(), 4.0 * (x.numel() + y.numel()) + (bits.numel() if bits is not None else 0),
-                 call, shape=(B, Cin, Cout, Hh, Ho, act)), "gt_conv3x3_resize_fwd")
+    # the channels-last entry takes the decision buffer behind the arguments of the planar one
+    _launch("gt_conv3x3_resize_fwd" + ("_nhwc" if out_nhwc else ""), x, w, y, B, Cin, Cout, Hh, Ww, Ho, Wo, drop, act,
+            *((bits,) if out_nhwc else ()), key="gt_conv3x3_resize_fwd", flops=2.0 * 36 * Cin * y.numel(),
+            nbytes=4.0 * (x.numel() + y.numel()) + (bits.numel() if bits is not None else 0),
+            shape=(B, Cin, Cout, Hh, Ho, act))
     return (y, bits) if want_bits else y
 
 
@@ -1060,17 +1060,14 @@ def conv3x3_wgrad_nhwc(gy: torch.Tensor, ldg: int, x: torch.Tensor, ldx: int, B:
     [B*H*W, >= Cout / Cin] whose row pitch is ldg / ldx (column segments of wider buffers are read in place).  Raises
     GtNotSupported for shapes the kernel does not take (the caller owns the fallback)."""
     need_f32_cuda(gy, x)
-    L = lib()
     prec = _precision[0] if precision is None else PREC_CODE[precision]
-    need = L.gt_conv3x3_wgrad_nhwc_ws_bytes(B, Hh, Ww, Cin, Cout)
+    need = lib().gt_conv3x3_wgrad_nhwc_ws_bytes(B, Hh, Ww, Cin, Cout)
     if need <= 0 or prec not in (PREC_BF16X3, PREC_F16X2):
         raise GtNotSupported("gt_conv3x3_wgrad_nhwc: " + _ERR[-4])
     ws = workspace(gy.device, need)
     dw = torch.empty(Cout, Cin, 3, 3, dtype=torch.float32, device=gy.device)
-    check(_timed("gt_conv3x3_wgrad_nhwc", 18.0 * B * Hh * Ww * Cin * Cout, 4.0 * B * Hh * Ww * (Cin + Cout),
-                 lambda: L.gt_conv3x3_wgrad_nhwc(gy.data_ptr(), ldg, x.data_ptr(), ldx, dw.data_ptr(), B, Hh, Ww, Cin, Cout,
-                                                 float(alpha), prec, ws.data_ptr(), ws.numel(), stream_ptr()),
-                 shape=(B, Hh, Ww, Cin, Cout)), "gt_conv3x3_wgrad_nhwc")
+    _launch("gt_conv3x3_wgrad_nhwc", gy, ldg, x, ldx, dw, B, Hh, Ww, Cin, Cout, float(alpha), prec, ws=ws,
+            flops=18.0 * B * Hh * Ww * Cin * Cout, nbytes=4.0 * B * Hh * Ww * (Cin + Cout), shape=(B, Hh, Ww, Cin, Cout))
     return dw
 
 
@@ -1079,7 +1076,7 @@ def debug_conv0_mask(mask: Optional[torch.Tensor]):
     decisions (gt_hip.h: gt_debug_conv0_mask) -- parity tests replay them in the float64 checker."""
     if mask is not None and (mask.dtype != torch.uint8 or not mask.is_cuda or not mask.is_contiguous()):
         raise TypeError("debug_conv0_mask: a contiguous uint8 device tensor")
-    check(lib().gt_debug_conv0_mask(ptr(mask), stream_ptr()), "gt_debug_conv0_mask")
+    check(lib().gt_debug_conv0_mask(ptr(mask), stream_ptr()), "gt_debug_conv0_mask")       # (not a Profile record)
 
 
 def conv3x3_resize_bwd(g: torch.Tensor, y: Optional[torch.Tensor], x: torch.Tensor, w: torch.Tensor,
@@ -1094,18 +1091,12 @@ def conv3x3_resize_bwd(g: torch.Tensor, y: Optional[torch.Tensor], x: torch.Tens
     Ho, Wo = (g.shape[1], g.shape[2]) if out_nhwc else (g.shape[2], g.shape[3])
     dw = torch.empty_like(w)
     ws = workspace(x.device, lib().gt_conv3x3_resize_bwd_ws_bytes(B, Cin, Cout, Hh, Ww))
-    dp = C.byref(drop) if (drop is not None and drop.p > 0) else None
-    if out_nhwc:
-        call = lambda: lib().gt_conv3x3_resize_bwd_nhwc(g.data_ptr(), ptr(y), x.data_ptr(), w.data_ptr(), B, Cin, Cout,
-                                                        Hh, Ww, Ho, Wo, dp, act, ptr(bits), dw.data_ptr(),
-                                                        ws.data_ptr(), ws.numel(), stream_ptr())
-    else:
-        call = lambda: lib().gt_conv3x3_resize_bwd(g.data_ptr(), ptr(y), x.data_ptr(), w.data_ptr(), B, Cin, Cout, Hh,
-                                                   Ww, Ho, Wo, dp, act, dw.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                   stream_ptr())
     reads_y = bits is None and act == ACT_RELU
-    nbytes = 4.0 * (x.numel() + g.numel() * (2 if reads_y else 1)) + (bits.numel() if bits is not None else 0)
-    check(_timed("gt_conv3x3_resize_bwd", 0, nbytes, call, shape=(B, Cin, Cout, Hh, Ho, act)), "gt_conv3x3_resize_bwd")
+    # the channels-last entry takes the decision buffer in front of dw, otherwise the arguments of the planar one
+    _launch("gt_conv3x3_resize_bwd" + ("_nhwc" if out_nhwc else ""), g, y, x, w, B, Cin, Cout, Hh, Ww, Ho, Wo, drop, act,
+            *((bits,) if out_nhwc else ()), dw, ws=ws, key="gt_conv3x3_resize_bwd",
+            nbytes=4.0 * (x.numel() + g.numel() * (2 if reads_y else 1)) + (bits.numel() if bits is not None else 0),
+            shape=(B, Cin, Cout, Hh, Ho, act))
     return dw
 
 
@@ -1118,10 +1109,8 @@ def bilinear2d_seg_fwd(x: torch.Tensor, Cc: int, size, seg: int, segp: int, act:
     Ho, Wo = int(size[0]), int(size[1])
     y = torch.empty(B, Ho, Wo, Cc, dtype=torch.float32, device=x.device)
     dact = torch.empty_like(y) if (want_dact and act == ACT_SILU) else None
-    check(_timed("gt_bilinear2d_seg_fwd", 0, 4.0 * B * Cc * (Hi * Wi + Ho * Wo * (2 if dact is not None else 1)),
-                 lambda: lib().gt_bilinear2d_seg_fwd(x.data_ptr(), y.data_ptr(), B, Cc, Hi, Wi, Ho, Wo, act, seg, segp,
-                                                     ptr(dact), stream_ptr()), shape=(B, Cc, Hi, Ho, act)),
-          "gt_bilinear2d_seg_fwd")
+    _launch("gt_bilinear2d_seg_fwd", x, y, B, Cc, Hi, Wi, Ho, Wo, act, seg, segp, dact,
+            nbytes=4.0 * B * Cc * (Hi * Wi + Ho * Wo * (2 if dact is not None else 1)), shape=(B, Cc, Hi, Ho, act))
     return (y, dact) if want_dact else y
 
 
@@ -1133,11 +1122,8 @@ def bilinear2d_seg_bwd(g: torch.Tensor, y_saved: Optional[torch.Tensor], in_size
     B, Ho, Wo, Cc = g.shape
     Hi, Wi = int(in_size[0]), int(in_size[1])
     dx = torch.empty(B, Hi, Wi, 3 * segp, dtype=torch.float32, device=g.device)
-    check(_timed("gt_bilinear2d_seg_bwd", 0, 4.0 * B * Cc * (Hi * Wi + 2 * Ho * Wo),
-                 lambda: lib().gt_bilinear2d_seg_bwd(g.data_ptr(), ptr(y_saved), dx.data_ptr(), B, Cc, Hi, Wi, Ho, Wo,
-                                                     act, seg, segp, ptr(x_gate), int(bool(gate_mul)), stream_ptr()),
-                 shape=(B, Cc, Hi, Ho, act)),
-          "gt_bilinear2d_seg_bwd")
+    _launch("gt_bilinear2d_seg_bwd", g, y_saved, dx, B, Cc, Hi, Wi, Ho, Wo, act, seg, segp, x_gate, int(bool(gate_mul)),
+            nbytes=4.0 * B * Cc * (Hi * Wi + 2 * Ho * Wo), shape=(B, Cc, Hi, Ho, act))
     return dx
 
 
@@ -1155,22 +1141,16 @@ def galerkin_ktv(Kp: torch.Tensor, Vp: torch.Tensor, B: int, n: int, h: int, dk:
     DP = round4(dk + p)
     ns = lib().gt_galerkin_ktv_slabs(B, n)
     slabs = torch.empty(ns, B, h, DP, DP, dtype=torch.float32, device=Kp.device)
-    check(_timed("gt_galerkin_ktv", 2.0 * B * h * n * DP * DP, 8.0 * B * n * h * DP,
-                 lambda: lib().gt_galerkin_ktv_affine(Kp.data_ptr(), Vp.data_ptr(), ptr(gamma), ptr(beta), B, n, h, dk, p,
-                                                      slabs.data_ptr(), ns, stream_ptr()),
-                 shape=(B, n, h, dk, p)), "gt_galerkin_ktv")
+    _launch("gt_galerkin_ktv_affine", Kp, Vp, gamma, beta, B, n, h, dk, p, slabs, ns, key="gt_galerkin_ktv",
+            flops=2.0 * B * h * n * DP * DP, nbytes=8.0 * B * n * h * DP, shape=(B, n, h, dk, p))
     return slabs
-
-
-# kernels that exist and pass their CPU lane-model checks but have not been measured on hardware yet are opt-in:
 
 
 def galerkin_dkv(Kp, Vp, dM, dKp, dVp, B: int, n: int, h: int, DP: int):
     """dK' = V' dM^T, dV' = K' dM per (batch, head) in one streaming pass (gt_galerkin_dkv)."""
     need_f32_cuda(Kp, Vp, dM, dKp, dVp)
-    check(_timed("gt_galerkin_dkv", 4.0 * B * h * n * DP * DP, 16.0 * B * n * h * DP,
-                 lambda: lib().gt_galerkin_dkv(Kp.data_ptr(), Vp.data_ptr(), dM.data_ptr(), dKp.data_ptr(), dVp.data_ptr(),
-                                               B, n, h, DP, stream_ptr()), shape=(B, n, h, DP)), "gt_galerkin_dkv")
+    _launch("gt_galerkin_dkv", Kp, Vp, dM, dKp, dVp, B, n, h, DP,
+            flops=4.0 * B * h * n * DP * DP, nbytes=16.0 * B * n * h * DP, shape=(B, n, h, DP))
 
 
 def galerkin_dkv_ln_supported(dk: int, p: int, norm_mask: int) -> bool:
@@ -1192,11 +1172,9 @@ def galerkin_dkv_ln(Kp, Vp, dM, dQp, qkv, gamma, stats, B: int, n: int, h: int, 
     dbeta = torch.empty(2, h, dk, dtype=torch.float32, device=dev)
     ws = workspace(dev, lib().gt_galerkin_dkv_ln_ws_bytes(B, h, dk))
     DP = round4(dk + p)
-    check(_timed("gt_galerkin_dkv_ln", 4.0 * B * h * n * DP * DP, 4.0 * T * h * (3 * DP + 5 * dk),
-                 lambda: lib().gt_galerkin_dkv_ln_plain(Kp.data_ptr(), Vp.data_ptr(), dM.data_ptr(), ptr(dQp), ptr(qkv),
-                                                  gamma.data_ptr(), ptr(beta), stats.data_ptr(), B, n, h, dk, p, d_qkv.data_ptr(),
-                                                  dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                  stream_ptr()), shape=(B, n, h, DP)), "gt_galerkin_dkv_ln")
+    _launch("gt_galerkin_dkv_ln_plain", Kp, Vp, dM, dQp, qkv, gamma, beta, stats, B, n, h, dk, p, d_qkv, dgamma, dbeta,
+            ws=ws, key="gt_galerkin_dkv_ln", flops=4.0 * B * h * n * DP * DP, nbytes=4.0 * T * h * (3 * DP + 5 * dk),
+            shape=(B, n, h, DP))
     return d_qkv, dgamma, dbeta
 
 
@@ -1209,10 +1187,7 @@ def feature_softmax_fwd(X: torch.Tensor, rows: int, dk: int, p: int, out: Option
     """softmax over the dk + p columns of each of ``rows`` head-tile segments [rows, DP]; ``out=X`` runs in place."""
     need_f32_cuda(X, out)
     out = torch.empty_like(X) if out is None else out
-    DP = round4(dk + p)
-    check(_timed("gt_feature_softmax_fwd", 0, 8.0 * rows * DP,
-                 lambda: lib().gt_feature_softmax_fwd(X.data_ptr(), out.data_ptr(), rows, dk, p, stream_ptr()),
-                 shape=(rows, dk, p)), "gt_feature_softmax_fwd")
+    _launch("gt_feature_softmax_fwd", X, out, rows, dk, p, nbytes=8.0 * rows * round4(dk + p), shape=(rows, dk, p))
     return out
 
 
@@ -1221,10 +1196,7 @@ def feature_softmax_bwd(Y: torch.Tensor, dY: torch.Tensor, rows: int, dk: int, p
     """dX = Y .* (dY - sum_c Y .* dY) per segment; ``out=dY`` runs in place."""
     need_f32_cuda(Y, dY, out)
     out = torch.empty_like(dY) if out is None else out
-    DP = round4(dk + p)
-    check(_timed("gt_feature_softmax_bwd", 0, 12.0 * rows * DP,
-                 lambda: lib().gt_feature_softmax_bwd(Y.data_ptr(), dY.data_ptr(), out.data_ptr(), rows, dk, p, stream_ptr()),
-                 shape=(rows, dk, p)), "gt_feature_softmax_bwd")
+    _launch("gt_feature_softmax_bwd", Y, dY, out, rows, dk, p, nbytes=12.0 * rows * round4(dk + p), shape=(rows, dk, p))
     return out
 
 
@@ -1233,11 +1205,9 @@ def token_softmax_fwd(X: torch.Tensor, B: int, n: int, h: int, dk: int, p: int,
     """softmax over the n tokens of every (batch, head, column < dk + p) of head tiles [B*n, h, DP]; ``out=X``: in place."""
     need_f32_cuda(X, out)
     out = torch.empty_like(X) if out is None else out
-    DP = round4(dk + p)
     ws = workspace(X.device, max(16, lib().gt_token_softmax_ws_bytes(B, n, h, dk, p)))
-    check(_timed("gt_token_softmax_fwd", 0, 12.0 * B * n * h * DP,
-                 lambda: lib().gt_token_softmax_fwd(X.data_ptr(), out.data_ptr(), B, n, h, dk, p, ws.data_ptr(), ws.numel(),
-                                                    stream_ptr()), shape=(B, n, h, dk, p)), "gt_token_softmax_fwd")
+    _launch("gt_token_softmax_fwd", X, out, B, n, h, dk, p, ws=ws, nbytes=12.0 * B * n * h * round4(dk + p),
+            shape=(B, n, h, dk, p))
     return out
 
 
@@ -1246,11 +1216,9 @@ def token_softmax_bwd(Y: torch.Tensor, dY: torch.Tensor, B: int, n: int, h: int,
     """dX = Y .* (dY - sum_t Y .* dY) per column; ``out=dY`` runs in place."""
     need_f32_cuda(Y, dY, out)
     out = torch.empty_like(dY) if out is None else out
-    DP = round4(dk + p)
     ws = workspace(Y.device, max(16, lib().gt_token_softmax_ws_bytes(B, n, h, dk, p)))
-    check(_timed("gt_token_softmax_bwd", 0, 20.0 * B * n * h * DP,
-                 lambda: lib().gt_token_softmax_bwd(Y.data_ptr(), dY.data_ptr(), out.data_ptr(), B, n, h, dk, p, ws.data_ptr(),
-                                                    ws.numel(), stream_ptr()), shape=(B, n, h, dk, p)), "gt_token_softmax_bwd")
+    _launch("gt_token_softmax_bwd", Y, dY, out, B, n, h, dk, p, ws=ws, nbytes=20.0 * B * n * h * round4(dk + p),
+            shape=(B, n, h, dk, p))
     return out
 
 
@@ -1260,13 +1228,10 @@ def token_norm_fwd(X: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps
     (Y, stats [B, h, dk, 2] = (mean, rstd)); ``out=X`` runs in place."""
     need_f32_cuda(X, gamma, beta, out)
     out = torch.empty_like(X) if out is None else out
-    DP = round4(dk + p)
     stats = torch.empty(B, h, dk, 2, dtype=torch.float32, device=X.device)
     ws = workspace(X.device, max(16, lib().gt_token_norm_ws_bytes(B, n, h, dk, p)))
-    check(_timed("gt_token_norm_fwd", 0, 12.0 * B * n * h * DP,
-                 lambda: lib().gt_token_norm_fwd(X.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), out.data_ptr(),
-                                                 stats.data_ptr(), B, n, h, dk, p, ws.data_ptr(), ws.numel(), stream_ptr()),
-                 shape=(B, n, h, dk, p)), "gt_token_norm_fwd")
+    _launch("gt_token_norm_fwd", X, gamma, beta, float(eps), out, stats, B, n, h, dk, p, ws=ws,
+            nbytes=12.0 * B * n * h * round4(dk + p), shape=(B, n, h, dk, p))
     return out, stats
 
 
@@ -1281,12 +1246,9 @@ def token_norm_bwd(X: torch.Tensor, dY: torch.Tensor, gamma: torch.Tensor, stats
     dbeta = torch.empty(h, dk, dtype=torch.float32, device=X.device) if dbeta is None else dbeta
     if not (dgamma.is_contiguous() and dbeta.is_contiguous()):
         raise ValueError("token_norm_bwd: dgamma / dbeta must be contiguous")
-    DP = round4(dk + p)
     ws = workspace(X.device, max(16, lib().gt_token_norm_ws_bytes(B, n, h, dk, p)))
-    check(_timed("gt_token_norm_bwd", 0, 20.0 * B * n * h * DP,
-                 lambda: lib().gt_token_norm_bwd(X.data_ptr(), dY.data_ptr(), gamma.data_ptr(), stats.data_ptr(), out.data_ptr(),
-                                                 dgamma.data_ptr(), dbeta.data_ptr(), B, n, h, dk, p, ws.data_ptr(), ws.numel(),
-                                                 stream_ptr()), shape=(B, n, h, dk, p)), "gt_token_norm_bwd")
+    _launch("gt_token_norm_bwd", X, dY, gamma, stats, out, dgamma, dbeta, B, n, h, dk, p, ws=ws,
+            nbytes=20.0 * B * n * h * round4(dk + p), shape=(B, n, h, dk, p))
     return out, dgamma, dbeta
 
 
@@ -1307,11 +1269,8 @@ def mlp_head_fwd(x2, w1, b1, w2, b2, act: int, out, precision: Optional[str] = N
     need_f32_cuda(x2, w1, b1, w2, b2, out)
     T, K = x2.shape
     N, no = w1.shape[0], w2.shape[0]
-    prec = head_precision(precision)
-    check(_timed("gt_mlp_head_fwd", 2.0 * T * N * (K + no), 4.0 * T * (K + no),
-                 lambda: lib().gt_mlp_head_fwd(x2.data_ptr(), T, K, N, no, w1.data_ptr(), ptr(b1), w2.data_ptr(), ptr(b2),
-                                               act, prec, out.data_ptr(), stream_ptr()), shape=(T, K, N, no)),
-          "gt_mlp_head_fwd")
+    _launch("gt_mlp_head_fwd", x2, T, K, N, no, w1, b1, w2, b2, act, head_precision(precision), out,
+            flops=2.0 * T * N * (K + no), nbytes=4.0 * T * (K + no), shape=(T, K, N, no))
     return out
 
 
@@ -1321,13 +1280,10 @@ def mlp_head_bwd(x2, w1, b1, w2, act: int, g, dx, dw1, db1, dw2, db2, precision:
     T, K = x2.shape
     N, no = w1.shape[0], w2.shape[0]
     prec = head_precision(precision)
-    need = lib().gt_mlp_head_bwd_ws_bytes(T)
-    ws = workspace(x2.device, need)
-    check(_timed("gt_mlp_head_bwd", 2.0 * T * N * (3 * K + 2 * no), 4.0 * T * ((3 if dx_gate is not None else 2) * K + no),
-                 lambda: lib().gt_mlp_head_bwd_gated(x2.data_ptr(), T, K, N, no, w1.data_ptr(), ptr(b1), w2.data_ptr(), act,
-                                                     prec, g.data_ptr(), ptr(dx), ptr(dx_gate), dw1.data_ptr(), ptr(db1),
-                                                     ptr(dw2), ptr(db2), ws.data_ptr(), ws.numel(), stream_ptr()),
-                 shape=(T, K, N, no)), "gt_mlp_head_bwd")
+    ws = workspace(x2.device, lib().gt_mlp_head_bwd_ws_bytes(T))
+    _launch("gt_mlp_head_bwd_gated", x2, T, K, N, no, w1, b1, w2, act, prec, g, dx, dx_gate, dw1, db1, dw2, db2, ws=ws,
+            key="gt_mlp_head_bwd", flops=2.0 * T * N * (3 * K + 2 * no),
+            nbytes=4.0 * T * ((3 if dx_gate is not None else 2) * K + no), shape=(T, K, N, no))
 
 
 def dft_supported(n: int, P: int, C_: int, Co: int) -> bool:
@@ -1338,9 +1294,8 @@ def dft_supported(n: int, P: int, C_: int, Co: int) -> bool:
 def dft_analysis(F, X, Y, nb: int, n: int, P: int, C_: int):
     """Y[b] (P x C) = F^T X[b] for nb grid lines (gt_dft_analysis)."""
     need_f32_cuda(F, X, Y)
-    check(_timed("gt_dft_analysis", 2.0 * nb * n * P * C_, 4.0 * nb * (n + P) * C_,
-                 lambda: lib().gt_dft_analysis(F.data_ptr(), X.data_ptr(), Y.data_ptr(), nb, n, P, C_, stream_ptr()),
-                 shape=(nb, n, P, C_)), "gt_dft_analysis")
+    _launch("gt_dft_analysis", F, X, Y, nb, n, P, C_, flops=2.0 * nb * n * P * C_, nbytes=4.0 * nb * (n + P) * C_,
+            shape=(nb, n, P, C_))
     return Y
 
 
@@ -1349,12 +1304,10 @@ def dft_synthesis(F, Z, Y, nb: int, n: int, P: int, Co: int, X2, W2, C2: int, bi
     """Y[b] (n x Co) = act(F Z[b] + X2[b] W2 + bias) for nb grid lines (gt_dft_synthesis); out_gate [nb, n, Co]:
     Y *= silu'(out_gate) on the store (gt_dft_synthesis_gated)."""
     need_f32_cuda(F, Z, Y, X2, W2, bias, pre, out_gate)
-    check(_timed("gt_dft_synthesis", 2.0 * nb * n * (P + C2) * Co,
-                 4.0 * nb * (n * (C2 + Co * (2 if pre is not None or out_gate is not None else 1)) + P * Co),
-                 lambda: lib().gt_dft_synthesis_gated(F.data_ptr(), Z.data_ptr(), Y.data_ptr(), nb, n, P, Co, X2.data_ptr(),
-                                                      W2.data_ptr(), C2, ptr(bias), act, ptr(pre), ptr(out_gate),
-                                                      stream_ptr()),
-                 shape=(nb, n, P, Co, C2)), "gt_dft_synthesis")
+    _launch("gt_dft_synthesis_gated", F, Z, Y, nb, n, P, Co, X2, W2, C2, bias, act, pre, out_gate, key="gt_dft_synthesis",
+            flops=2.0 * nb * n * (P + C2) * Co,
+            nbytes=4.0 * nb * (n * (C2 + Co * (2 if pre is not None or out_gate is not None else 1)) + P * Co),
+            shape=(nb, n, P, Co, C2))
     return Y
 
 
@@ -1382,11 +1335,9 @@ def fourier16_presplit(tensors, B: int, n: int, h: int, DP: int):
     if nb <= 0:
         raise GtNotSupported(f"gt_fourier16: head tile width {DP}")
     imgs = [torch.empty(nb, dtype=torch.uint8, device=tensors[0].device) for _ in tensors]
-    xs = [t.data_ptr() for t in tensors] + [None] * (4 - len(tensors))
-    is_ = [t.data_ptr() for t in imgs] + [None] * (4 - len(tensors))
-    check(_timed("gt_fourier16_presplit", 0.0, len(tensors) * (4.0 * B * n * h * DP + nb),
-                 lambda: lib().gt_fourier16_presplit(*xs, *is_, B, n, h, DP, stream_ptr()),
-                 shape=(B, n, h, DP, len(tensors))), "gt_fourier16_presplit")
+    unused = [None] * (4 - len(tensors))
+    _launch("gt_fourier16_presplit", *tensors, *unused, *imgs, *unused, B, n, h, DP,
+            nbytes=len(tensors) * (4.0 * B * n * h * DP + nb), shape=(B, n, h, DP, len(tensors)))
     return imgs
 
 
@@ -1400,8 +1351,7 @@ def dropout_block16(S: torch.Tensor, BH: int, n: int, drop) -> torch.Tensor:
     """In place: S[bh, q, k] *= keep(q, k) / (1 - p) with the block mask of gt_fourier16_attn(block16 = 1)."""
     need_f32_cuda(S)
     assert S.is_contiguous() and S.numel() == BH * n * n
-    check(_timed("gt_dropout_block16", 0.0, 8.0 * S.numel(),
-                 lambda: lib().gt_dropout_block16(S.data_ptr(), BH, n, C.byref(drop), stream_ptr())), "gt_dropout_block16")
+    _launch("gt_dropout_block16", S, BH, n, C.byref(drop), nbytes=8.0 * S.numel())      # (by reference whatever its p)
     return S
 
 
@@ -1417,13 +1367,10 @@ def fourier16_attn(F1, F2, T1, T2, B: int, n: int, h: int, DP: int, scale: float
     if O2 is None and F2 is not None:
         O2 = torch.empty_like(O1)
     need_f32_cuda(mask, O1, O2)
-    dp = C.byref(drop) if (drop is not None and drop.p > 0) else None
     nprod = 2 if F2 is not None else 1
-    check(_timed("gt_fourier16_attn", 4.0 * nprod * B * h * n * n * DP, 4.0 * (3 + nprod) * B * n * h * DP,
-                 lambda: lib().gt_fourier16_attn(F1.data_ptr(), ptr(F2), T1.data_ptr(), T2.data_ptr(), O1.data_ptr(),
-                                                 ptr(O2), B, n, h, DP, scale, ptr(mask), dp, int(bool(block16)),
-                                                 int(owner_is_key), stream_ptr()), shape=(B, n, h, DP, nprod)),
-          "gt_fourier16_attn")
+    _launch("gt_fourier16_attn", F1, F2, T1, T2, O1, O2, B, n, h, DP, scale, mask, drop, int(bool(block16)),
+            int(owner_is_key), flops=4.0 * nprod * B * h * n * n * DP, nbytes=4.0 * (3 + nprod) * B * n * h * DP,
+            shape=(B, n, h, DP, nprod))
     return (O1, O2) if F2 is not None else O1
 
 
@@ -1442,13 +1389,9 @@ def fourier_attn(F1, F2, T1, T2, B: int, n: int, h: int, DP: int, scale: float, 
         O1 = torch.empty(B * n, h, DP, dtype=torch.float32, device=F1.device)
     if O2 is None and F2 is not None:
         O2 = torch.empty_like(O1)
-    dp = C.byref(drop) if (drop is not None and drop.p > 0) else None
     nprod = 2 if F2 is not None else 1
-    sym = _fourier_sym(DP)
-    check(_timed(sym, 4.0 * nprod * B * h * n * n * DP, 4.0 * (3 + nprod) * B * n * h * DP,
-                 lambda: getattr(lib(), sym)(F1.data_ptr(), ptr(F2), T1.data_ptr(), T2.data_ptr(), O1.data_ptr(),
-                                             ptr(O2), B, n, h, DP, scale, ptr(mask), dp, int(owner_is_key),
-                                             stream_ptr()), shape=(B, n, h, DP, nprod)), sym)
+    _launch(_fourier_sym(DP), F1, F2, T1, T2, O1, O2, B, n, h, DP, scale, mask, drop, int(owner_is_key),
+            flops=4.0 * nprod * B * h * n * n * DP, nbytes=4.0 * (3 + nprod) * B * n * h * DP, shape=(B, n, h, DP, nprod))
     return (O1, O2) if F2 is not None else O1
 
 
@@ -1463,10 +1406,6 @@ def _softmax_sym(DP: int, tail: str) -> str:
     return ("gt_softmax_attn_wide_" if DP in SOFTMAX_DP_WIDE else "gt_softmax_attn_") + tail
 
 
-def _drop_ref(drop):
-    return C.byref(drop) if (drop is not None and drop.p > 0) else None
-
-
 def softmax_attn_fwd(Q, K, V, B: int, n: int, h: int, DP: int, scale: float, mask, drop, O=None, L=None):
     """gt_softmax_attn_fwd (DP 68 / 100: gt_softmax_attn_wide_fwd) on head tiles [B*n, h, DP]: returns (O, L), L [2, B, h, n]:
     L[0] = row maximum + log row sum, L[1] its rounding residual (gt_hip.h)."""
@@ -1475,11 +1414,8 @@ def softmax_attn_fwd(Q, K, V, B: int, n: int, h: int, DP: int, scale: float, mas
         O = torch.empty(B * n, h, DP, dtype=torch.float32, device=Q.device)
     if L is None:
         L = torch.empty(2, B, h, n, dtype=torch.float32, device=Q.device)
-    sym = _softmax_sym(DP, "fwd")
-    check(_timed(sym, 4.0 * B * h * n * n * DP, 16.0 * B * n * h * DP,
-                 lambda: getattr(lib(), sym)(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), B, n, h, DP,
-                                             scale, ptr(mask), _drop_ref(drop), stream_ptr()),
-                 shape=(B, n, h, DP)), sym)
+    _launch(_softmax_sym(DP, "fwd"), Q, K, V, O, L, B, n, h, DP, scale, mask, drop,
+            flops=4.0 * B * h * n * n * DP, nbytes=16.0 * B * n * h * DP, shape=(B, n, h, DP))
     return O, L
 
 
@@ -1491,17 +1427,10 @@ def softmax_attn_bwd(dO, O, Q, K, V, L, B: int, n: int, h: int, DP: int, scale: 
     dev = Q.device
     dQ, dK, dV = (torch.empty(B * n, h, DP, dtype=torch.float32, device=dev) if t is None else t for t in (dQ, dK, dV))
     D = torch.empty(B, h, n, dtype=torch.float32, device=dev)
-    sym_q, sym_kv = _softmax_sym(DP, "bwd_q"), _softmax_sym(DP, "bwd_kv")
-    check(_timed(sym_q, 6.0 * B * h * n * n * DP, 24.0 * B * n * h * DP,
-                 lambda: getattr(lib(), sym_q)(dO.data_ptr(), O.data_ptr(), Q.data_ptr(), K.data_ptr(), V.data_ptr(),
-                                               L.data_ptr(), D.data_ptr(), dQ.data_ptr(), B, n, h, DP, scale, ptr(mask),
-                                               _drop_ref(drop), stream_ptr()), shape=(B, n, h, DP)),
-          sym_q)
-    check(_timed(sym_kv, 8.0 * B * h * n * n * DP, 24.0 * B * n * h * DP,
-                 lambda: getattr(lib(), sym_kv)(K.data_ptr(), V.data_ptr(), Q.data_ptr(), dO.data_ptr(), L.data_ptr(),
-                                                D.data_ptr(), dK.data_ptr(), dV.data_ptr(), B, n, h, DP, scale,
-                                                ptr(mask), _drop_ref(drop), stream_ptr()), shape=(B, n, h, DP)),
-          sym_kv)
+    _launch(_softmax_sym(DP, "bwd_q"), dO, O, Q, K, V, L, D, dQ, B, n, h, DP, scale, mask, drop,
+            flops=6.0 * B * h * n * n * DP, nbytes=24.0 * B * n * h * DP, shape=(B, n, h, DP))
+    _launch(_softmax_sym(DP, "bwd_kv"), K, V, Q, dO, L, D, dK, dV, B, n, h, DP, scale, mask, drop,
+            flops=8.0 * B * h * n * n * DP, nbytes=24.0 * B * n * h * DP, shape=(B, n, h, DP))
     return dQ, dK, dV, D
 
 
@@ -1512,10 +1441,8 @@ def row_softmax_fwd(S, rows: int, n: int, mask, drop, P=None, Pm=None, row0: int
     if P is None:
         P = torch.empty_like(S)
     if Pm is None:
-        Pm = torch.empty_like(S) if (mask is not None or _drop_ref(drop) is not None) else P
-    check(_timed("gt_row_softmax_fwd", 0.0, 12.0 * S.numel(),
-                 lambda: lib().gt_row_softmax_fwd(S.data_ptr(), P.data_ptr(), Pm.data_ptr(), rows, n, row0, ptr(mask),
-                                                  _drop_ref(drop), stream_ptr())), "gt_row_softmax_fwd")
+        Pm = torch.empty_like(S) if (mask is not None or (drop is not None and drop.p > 0)) else P
+    _launch("gt_row_softmax_fwd", S, P, Pm, rows, n, row0, mask, drop, nbytes=12.0 * S.numel())
     return P, Pm
 
 
@@ -1525,7 +1452,5 @@ def row_softmax_bwd(P, dPm, rows: int, n: int, mask, drop, dS=None, row0: int = 
     assert P.is_contiguous() and dPm.is_contiguous() and P.numel() == rows * n
     if dS is None:
         dS = torch.empty_like(P)
-    check(_timed("gt_row_softmax_bwd", 0.0, 12.0 * P.numel(),
-                 lambda: lib().gt_row_softmax_bwd(P.data_ptr(), dPm.data_ptr(), dS.data_ptr(), rows, n, row0, ptr(mask),
-                                                  _drop_ref(drop), stream_ptr())), "gt_row_softmax_bwd")
+    _launch("gt_row_softmax_bwd", P, dPm, dS, rows, n, row0, mask, drop, nbytes=12.0 * P.numel())
     return dS

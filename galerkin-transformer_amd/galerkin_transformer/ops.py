@@ -1171,6 +1171,33 @@ def _project_heads_bwd(s, dO3, ln, g_in, in_mask, dims, norm_mask, token_norm, h
     return dx, dwqkv, dbqkv, dgamma, dbeta
 
 
+def _merged_fc_fwd(att, out, rc, wf, bfc, d_out, dims, sign):
+    """fc over the merged heads, shared by the fourier and softmax cores: out = res + sign * dropout(fc(att)) from the head
+    outputs att [T, h*DP].  Returns wpad [d, h*DP], the fc weight with zero columns under the tiles' padding (saved for
+    _merged_fc_bwd)."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    T, hD = B * n, h * DP
+    wpad = torch.zeros(d, h, DP, dtype=torch.float32, device=out.device)
+    wpad[:, :, :Dr] = wf.reshape(d, h, Dr)
+    wpad = wpad.reshape(d, hD)
+    H.gemm(att, wpad, out, T, d, hD, lda=hD, ldb=hD, ldc=d, bias=bfc, drop=d_out, res=rc, ldr=d, out_scale=sign)
+    return wpad
+
+
+def _merged_fc_bwd(s, g, dims, sign, hbf):
+    """Backward of _merged_fc_fwd from the masked gradient g [T, d], s.att and s.wpad: (datt [T, h*DP], dwfc, dbfc)."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    T, hD, dev = B * n, h * DP, g.device
+    dwpad = torch.empty(d, hD, dtype=torch.float32, device=dev)
+    dbfc = torch.empty(d, dtype=torch.float32, device=dev) if hbf else None
+    H.gemm(g, s.att, dwpad, d, hD, T, layout_a=1, layout_b=1, lda=d, ldb=hD, ldc=hD, split_k=0, alpha=sign,
+           a_colsum=dbfc, a_drop_sign=sign)     # (alpha signs the product, a_drop_sign the column sums)
+    dwfc = dwpad.reshape(d, h, DP)[:, :, :Dr].reshape(d, h * Dr)
+    datt = torch.empty(T, hD, dtype=torch.float32, device=dev)
+    H.gemm(g, s.wpad, datt, T, hD, d, layout_b=1, lda=d, ldb=hD, ldc=hD, alpha=sign)
+    return datt, dwfc, dbfc
+
+
 def _galerkin_fwd(kind, Qp, Kp, Vp, out, rc, wf, bfc, affine, mask, d_attn, d_out, dims, sign):
     """galerkin / linear core: M = mask .* (K'^T V')/n, out = res + sign * dropout(fc(Q' M)).  ``affine`` = (gamma, beta) for
     "plain" tiles, else (None, None).  Returns (attn_weight, tensors to save)."""
@@ -1256,10 +1283,8 @@ def _fourier_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn, d_out, dims, sign, 
     tensors to save, (flash, f16, block16)): the route, decided once here; the backward follows it."""
     B, n, d, h, dk, p, Dr, DP = dims
     T, hD, dev = B * n, h * DP, out.device
+    hd_bs, nn_bs = (n * hD, DP), (h * n * n, n * n)      # batch strides over (sample, head): head tiles, n x n matrices
     scale = 1.0 / math.sqrt(Dr) / n
-    wpad = torch.zeros(d, h, DP, dtype=torch.float32, device=dev)
-    wpad[:, :, :Dr] = wf.reshape(d, h, Dr)
-    wpad = wpad.reshape(d, hD)
     # fp16 arithmetic active: every width of the fp16 kernel runs on it; otherwise (f32 / bf16 modes) the fp32-MFMA kernel,
     # which has the same widths behind two entry points (H.fourier_attn picks)
     flash = (not need_w) and (DP in H.FOURIER_DP + H.FOURIER_DP_WIDE or (DP in H.FOURIER16_DP and H.fourier16_active()))
@@ -1277,17 +1302,14 @@ def _fourier_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn, d_out, dims, sign, 
         att = H.fourier_attn(Qp, None, Kp, Vp, B, n, h, DP, scale, mask, d_attn, False).reshape(T, hD)
     else:
         S = torch.empty(B, h, n, n, dtype=torch.float32, device=dev)
-        H.gemm(Qp, Kp, S, n, n, DP, lda=hD, ldb=hD, ldc=n, batch=(B, h), a_bs=(n * hD, DP),
-               b_bs=(n * hD, DP), c_bs=(h * n * n, n * n), alpha=scale, drop=None if block16 else d_attn,
-               aux_op=H.AUX_MUL if mask is not None else H.AUX_NONE, aux=mask, ldaux=n,
-               aux_bs=(h * n * n, n * n))
+        H.gemm(Qp, Kp, S, n, n, DP, lda=hD, ldb=hD, ldc=n, batch=(B, h), a_bs=hd_bs, b_bs=hd_bs, c_bs=nn_bs, alpha=scale,
+               drop=None if block16 else d_attn, aux_op=H.AUX_MUL if mask is not None else H.AUX_NONE, aux=mask, ldaux=n,
+               aux_bs=nn_bs)
         if block16:
             H.dropout_block16(S, B * h, n, d_attn)
         att = torch.empty(T, hD, dtype=torch.float32, device=dev)
-        H.gemm(S, Vp, att, n, DP, n, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h),
-               a_bs=(h * n * n, n * n), b_bs=(n * hD, DP), c_bs=(n * hD, DP))
-    H.gemm(att, wpad, out, T, d, hD, lda=hD, ldb=hD, ldc=d, bias=bfc, drop=d_out, res=rc, ldr=d,
-           out_scale=sign)
+        H.gemm(S, Vp, att, n, DP, n, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs, b_bs=hd_bs, c_bs=hd_bs)
+    wpad = _merged_fc_fwd(att, out, rc, wf, bfc, d_out, dims, sign)
     attn_w = S if S is not None else torch.empty(0, device=dev)
     return attn_w, dict(wpad=wpad, S=S, att=att, iq=iq, ik=ik, iv=iv), (flash, f16, block16)
 
@@ -1296,16 +1318,11 @@ def _fourier_bwd(s, g, d_attn, dims, sign, hbf, flash, f16, block16):
     """Backward of _fourier_fwd on the route it took.  Returns (dO3, dwfc, dbfc)."""
     B, n, d, h, dk, p, Dr, DP = dims
     T, hD, dev = B * n, h * DP, g.device
+    hd_bs, nn_bs = (n * hD, DP), (h * n * n, n * n)      # batch strides over (sample, head): head tiles, n x n matrices
     dO3 = torch.empty(3, T, h, DP, dtype=torch.float32, device=dev)
     Qp, Kp, Vp = s.out3[0], s.out3[1], s.out3[2]
     scale = 1.0 / math.sqrt(Dr) / n
-    dwpad = torch.empty(d, hD, dtype=torch.float32, device=dev)
-    dbfc = torch.empty(d, dtype=torch.float32, device=dev) if hbf else None
-    H.gemm(g, s.att, dwpad, d, hD, T, layout_a=1, layout_b=1, lda=d, ldb=hD, ldc=hD, split_k=0, alpha=sign,
-           a_colsum=dbfc, a_drop_sign=sign)     # (alpha signs the product, a_drop_sign the column sums)
-    dwfc = dwpad.reshape(d, h, DP)[:, :, :Dr].reshape(d, h * Dr)
-    datt = torch.empty(T, hD, dtype=torch.float32, device=dev)
-    H.gemm(g, s.wpad, datt, T, hD, d, layout_b=1, lda=d, ldb=hD, ldc=hD, alpha=sign)
+    datt, dwfc, dbfc = _merged_fc_bwd(s, g, dims, sign, hbf)
     datt3 = datt.reshape(T, h, DP)
     if f16:       # fused passes: dQ' = (dO V'^T .* m) K' ;  dV' = (S .* m)^T dO, dK' = (dO V'^T .* m)^T Q'
         (ido,) = H.fourier16_presplit((datt3,), B, n, h, DP)
@@ -1317,19 +1334,17 @@ def _fourier_bwd(s, g, d_attn, dims, sign, hbf, flash, f16, block16):
         H.fourier_attn(Kp, Vp, Qp, datt3, B, n, h, DP, scale, s.mask, d_attn, True, O1=dO3[2], O2=dO3[1])
     else:
         dS = torch.empty(B, h, n, n, dtype=torch.float32, device=dev)
-        H.gemm(datt, Vp, dS, n, n, DP, lda=hD, ldb=hD, ldc=n, batch=(B, h), a_bs=(n * hD, DP),
-               b_bs=(n * hD, DP), c_bs=(h * n * n, n * n), alpha=scale, drop=None if block16 else d_attn,
-               aux_op=H.AUX_MUL if s.mask is not None else H.AUX_NONE, aux=s.mask, ldaux=n,
-               aux_bs=(h * n * n, n * n))
+        H.gemm(datt, Vp, dS, n, n, DP, lda=hD, ldb=hD, ldc=n, batch=(B, h), a_bs=hd_bs, b_bs=hd_bs, c_bs=nn_bs, alpha=scale,
+               drop=None if block16 else d_attn, aux_op=H.AUX_MUL if s.mask is not None else H.AUX_NONE, aux=s.mask, ldaux=n,
+               aux_bs=nn_bs)
         if block16:
             H.dropout_block16(dS, B * h, n, d_attn)
         # dV' = S^T datt ; dQ' = dS K' ; dK' = dS^T Q'
-        H.gemm(s.S, datt, dO3[2], n, DP, n, layout_a=1, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h),
-               a_bs=(h * n * n, n * n), b_bs=(n * hD, DP), c_bs=(n * hD, DP))
-        H.gemm(dS, Kp, dO3[0], n, DP, n, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h),
-               a_bs=(h * n * n, n * n), b_bs=(n * hD, DP), c_bs=(n * hD, DP))
-        H.gemm(dS, Qp, dO3[1], n, DP, n, layout_a=1, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h),
-               a_bs=(h * n * n, n * n), b_bs=(n * hD, DP), c_bs=(n * hD, DP))
+        H.gemm(s.S, datt, dO3[2], n, DP, n, layout_a=1, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs,
+               b_bs=hd_bs, c_bs=hd_bs)
+        H.gemm(dS, Kp, dO3[0], n, DP, n, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs, b_bs=hd_bs, c_bs=hd_bs)
+        H.gemm(dS, Qp, dO3[1], n, DP, n, layout_a=1, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs,
+               b_bs=hd_bs, c_bs=hd_bs)
     return dO3, dwfc, dbfc
 
 
@@ -1341,10 +1356,8 @@ def _softmax_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn, d_out, dims, sign, 
     follows it."""
     B, n, d, h, dk, p, Dr, DP = dims
     T, hD, dev = B * n, h * DP, out.device
+    hd_bs, nn_bs = (n * hD, DP), (h * n * n, n * n)      # batch strides over (sample, head): head tiles, n x n matrices
     scale = 1.0 / math.sqrt(Dr)
-    wpad = torch.zeros(d, h, DP, dtype=torch.float32, device=dev)
-    wpad[:, :, :Dr] = wf.reshape(d, h, Dr)
-    wpad = wpad.reshape(d, hD)
     flash = not need_w
     P = Pm = L = None
     if flash:
@@ -1352,13 +1365,13 @@ def _softmax_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn, d_out, dims, sign, 
         att = att.reshape(T, hD)
     else:
         P = torch.empty(B, h, n, n, dtype=torch.float32, device=dev)
-        H.gemm(Qp, Kp, P, n, n, DP, lda=hD, ldb=hD, ldc=n, batch=(B, h), a_bs=(n * hD, DP), b_bs=(n * hD, DP),
-               c_bs=(h * n * n, n * n), alpha=scale, precision="f32")
+        H.gemm(Qp, Kp, P, n, n, DP, lda=hD, ldb=hD, ldc=n, batch=(B, h), a_bs=hd_bs, b_bs=hd_bs, c_bs=nn_bs, alpha=scale,
+               precision="f32")
         P, Pm = H.row_softmax_fwd(P, B * h * n, n, mask, d_attn, P=P)      # in place; Pm is P without mask and dropout
         att = torch.empty(T, hD, dtype=torch.float32, device=dev)
-        H.gemm(Pm, Vp, att, n, DP, n, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=(h * n * n, n * n),
-               b_bs=(n * hD, DP), c_bs=(n * hD, DP), precision="f32")
-    H.gemm(att, wpad, out, T, d, hD, lda=hD, ldb=hD, ldc=d, bias=bfc, drop=d_out, res=rc, ldr=d, out_scale=sign)
+        H.gemm(Pm, Vp, att, n, DP, n, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs, b_bs=hd_bs, c_bs=hd_bs,
+               precision="f32")
+    wpad = _merged_fc_fwd(att, out, rc, wf, bfc, d_out, dims, sign)
     attn_w = Pm if Pm is not None else torch.empty(0, device=dev)
     return attn_w, dict(wpad=wpad, att=att, L=L, P=P, Pm=Pm), flash
 
@@ -1367,32 +1380,26 @@ def _softmax_bwd(s, g, d_attn, dims, sign, hbf, flash):
     """Backward of _softmax_fwd on the route it took.  Returns (dO3, dwfc, dbfc)."""
     B, n, d, h, dk, p, Dr, DP = dims
     T, hD, dev = B * n, h * DP, g.device
+    hd_bs, nn_bs = (n * hD, DP), (h * n * n, n * n)      # batch strides over (sample, head): head tiles, n x n matrices
     dO3 = torch.empty(3, T, h, DP, dtype=torch.float32, device=dev)
     Qp, Kp, Vp = s.out3[0], s.out3[1], s.out3[2]
     scale = 1.0 / math.sqrt(Dr)
-    dwpad = torch.empty(d, hD, dtype=torch.float32, device=dev)
-    dbfc = torch.empty(d, dtype=torch.float32, device=dev) if hbf else None
-    H.gemm(g, s.att, dwpad, d, hD, T, layout_a=1, layout_b=1, lda=d, ldb=hD, ldc=hD, split_k=0, alpha=sign,
-           a_colsum=dbfc, a_drop_sign=sign)     # (alpha signs the product, a_drop_sign the column sums)
-    dwfc = dwpad.reshape(d, h, DP)[:, :, :Dr].reshape(d, h * Dr)
-    datt = torch.empty(T, hD, dtype=torch.float32, device=dev)
-    H.gemm(g, s.wpad, datt, T, hD, d, layout_b=1, lda=d, ldb=hD, ldc=hD, alpha=sign)
+    datt, dwfc, dbfc = _merged_fc_bwd(s, g, dims, sign, hbf)
     if flash:     # dQ' (and D), then dK', dV': P = exp(S - L) recomputed tile by tile
         H.softmax_attn_bwd(datt.reshape(T, h, DP), s.att.reshape(T, h, DP), Qp, Kp, Vp, s.L, B, n, h, DP, scale, s.mask,
                            d_attn, dQ=dO3[0], dK=dO3[1], dV=dO3[2])
     else:
-        nn_bs = (h * n * n, n * n)
         dS = torch.empty(B, h, n, n, dtype=torch.float32, device=dev)
-        H.gemm(datt, Vp, dS, n, n, DP, lda=hD, ldb=hD, ldc=n, batch=(B, h), a_bs=(n * hD, DP), b_bs=(n * hD, DP),
+        H.gemm(datt, Vp, dS, n, n, DP, lda=hD, ldb=hD, ldc=n, batch=(B, h), a_bs=hd_bs, b_bs=hd_bs,
                c_bs=nn_bs, precision="f32")                                # dPm = dO V'^T
         H.row_softmax_bwd(s.P, dS, B * h * n, n, s.mask, d_attn, dS=dS)     # dS = P .* (m .* dPm - sum P m dPm), in place
         # dV' = Pm^T datt ; dQ' = dS K' / sqrt(d_k') ; dK' = dS^T Q' / sqrt(d_k')
         H.gemm(s.Pm, datt, dO3[2], n, DP, n, layout_a=1, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs,
-               b_bs=(n * hD, DP), c_bs=(n * hD, DP), precision="f32")
+               b_bs=hd_bs, c_bs=hd_bs, precision="f32")
         H.gemm(dS, Kp, dO3[0], n, DP, n, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs,
-               b_bs=(n * hD, DP), c_bs=(n * hD, DP), alpha=scale, precision="f32")
+               b_bs=hd_bs, c_bs=hd_bs, alpha=scale, precision="f32")
         H.gemm(dS, Qp, dO3[1], n, DP, n, layout_a=1, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs,
-               b_bs=(n * hD, DP), c_bs=(n * hD, DP), alpha=scale, precision="f32")
+               b_bs=hd_bs, c_bs=hd_bs, alpha=scale, precision="f32")
     return dO3, dwfc, dbfc
 
 
@@ -1410,7 +1417,8 @@ class SimpleAttentionFn(Function):
 
     One autograd node in two stages.  forward: _project_heads (QKV projection, head norm, token norm; shared), then the core
     of the kind, _galerkin_fwd (galerkin, linear), _fourier_fwd or _softmax_fwd, which ends in the fc product that writes
-    ``out``.  backward: _galerkin_bwd / _fourier_bwd / _softmax_bwd, then _project_heads_bwd.  Forward to backward: the tensors go by name through
+    ``out`` (fourier and softmax share that stage: _merged_fc_fwd / _merged_fc_bwd; galerkin folds fc into P).  backward:
+    _galerkin_bwd / _fourier_bwd / _softmax_bwd, then _project_heads_bwd.  Forward to backward: the tensors go by name through
     _save_named / _saved; ctx.cfg, ctx.dims, ctx.salt, ctx.has (bqkv, bfc, res given), ctx.xshape and ctx.in_mask carry the
     call; ctx.plain, ctx.fused_ln and, for fourier, ctx.flash, ctx.f16, ctx.block16 (softmax: ctx.flash) record every route the forward chose.
     The backward follows them and consults no module-level switch."""

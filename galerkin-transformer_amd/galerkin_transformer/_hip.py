@@ -1127,6 +1127,20 @@ def bilinear2d_seg_bwd(g: torch.Tensor, y_saved: Optional[torch.Tensor], in_size
     return dx
 
 
+RS_MAXT = 6          # gt_resize.hip: output rows / columns per input cell that the resize backward holds in registers
+
+
+def bilinear2d_seg_supported(C: int, seg: int, segp: int, in_size, out_size) -> bool:
+    """Shapes of gt_bilinear2d_seg_fwd / _bwd (gt_resize.hip: check_seg, taps_fit): C real channels in three column
+    segments of widths (seg, seg, C - 2 seg), each padded to segp; an even seg; and in the backward at most RS_MAXT
+    contributing outputs per input cell on either axis, i.e. an up-sampling factor below ~2."""
+    def taps_fit(ni, no):
+        return no <= RS_MAXT if ni <= 1 else 2.0 * (no - 1) / (ni - 1) + 2.0 <= RS_MAXT
+    if seg <= 0 or seg & 1 or segp < seg or segp & 3 or C & 3 or C <= 2 * seg or C - 2 * seg > segp:
+        return False
+    return taps_fit(in_size[0], out_size[0]) and taps_fit(in_size[1], out_size[1])
+
+
 def galerkin_ktv_supported(dk: int, p: int) -> bool:
     return not (dk % 16 or dk > 96 or dk // 16 == 5 or p > 2)
 

@@ -19,6 +19,7 @@ from torch import nn
 from torch.nn.init import constant_, xavier_normal_, xavier_uniform_
 from torch.nn.parameter import Parameter
 
+from . import _hip as H
 from . import ops, spectral
 from .ops import get_attention_dropout, push_attention_masks, set_attention_dropout  # noqa: F401
 
@@ -142,10 +143,7 @@ def _resize(x, size, act_module=None, in_nhwc=False, out_nhwc=False):
     """activation(F.interpolate(x, ..., mode='bilinear', align_corners=True)) on the HIP resize kernel;
     a ReLU is fused into the kernel, any other activation is applied on its output."""
     name = "none" if act_module is None else _act_name(act_module)
-    if isinstance(size, (tuple, list)) and isinstance(size[0], float):
-        raise NotImplementedError("per-axis scale factors")
-    y = ops.bilinear_resize(x, size if isinstance(size, float) else tuple(size), in_nhwc, out_nhwc,
-                            act="relu" if name == "relu" else None)
+    y = ops.bilinear_resize(x, size, in_nhwc, out_nhwc, act="relu" if name == "relu" else None)
     return y if name in ("relu", "none") else act_module(y)
 
 
@@ -186,11 +184,11 @@ class Interp2dEncoder(nn.Module):
         gradient, with ReLU (or SiLU, round 6) on both sides of the resize: the case gt_conv3x3_resize_* implements."""
         c = self.conv0
         cv = c.conv[0]
-        size = self.interp_size[0]
-        size_ok = isinstance(size, float) or (isinstance(size, (tuple, list)) and not isinstance(size[0], float))
-        return (size_ok and self._fused_act((c,)) is not None
-                and not c.add_res and not c.basic_block and cv.kernel_size == (3, 3) and cv.padding == (1, 1)
-                and cv.stride == (1, 1) and cv.dilation == (1, 1) and cv.groups == 1 and cv.bias is None
+        try:
+            ops.out_size(x.shape[2], x.shape[3], self.interp_size[0])
+        except NotImplementedError:     # per-axis scale factors
+            return False
+        return (self._fused_act((c,)) is not None and not c.add_res and not c.basic_block and ops._plain_conv3x3(cv)
                 and cv.in_channels <= 4 and x.is_cuda and not (torch.is_grad_enabled() and x.requires_grad))
 
     def _chain_ok(self, x, out_nhwc) -> bool:
@@ -202,32 +200,21 @@ class Interp2dEncoder(nn.Module):
                 and all(c.plain() for c in cs)
                 and len({c.conv[1].p for c in cs}) == 1):
             return False
-        s0 = self.interp_size[0]
-        if isinstance(s0, float):
-            h1, w1 = int(math.floor(x.shape[2] * s0)), int(math.floor(x.shape[3] * s0))
-        elif isinstance(s0, (tuple, list)) and not isinstance(s0[0], float):
-            h1, w1 = int(s0[0]), int(s0[1])
-        else:
+        try:
+            h1, w1 = ops.out_size(x.shape[2], x.shape[3], self.interp_size[0])
+            h2, w2 = ops.out_size(h1, w1, self.interp_size[1])
+        except NotImplementedError:     # per-axis scale factors
             return False
         if x.shape[0] * h1 * w1 < 1024 or w1 < 3 or h1 < 3:       # (16 384 until round 5: C2 at B <= 2 fell back to the library)
             return False
         convs = [c.conv[0] for c in cs]
         widths = [c.out_channels for c in convs]
         cp = (max(widths) + 15) // 16 * 16
-        size = self.interp_size[1]
-        if isinstance(size, float):
-            h2, w2 = int(math.floor(h1 * size)), int(math.floor(w1 * size))
-        elif isinstance(size, (tuple, list)) and not isinstance(size[0], float):
-            h2, w2 = int(size[0]), int(size[1])
-        else:
-            return False
-        # what the segment resize kernels take (gt_resize.hip: check_seg, taps_fit): an even segment width (out_dim = 112 /
-        # 160 give 37 / 53: those run the conv1 / conv2 / conv3 + cat path below), and in the backward at most RS_MAXT = 6
-        # output rows / columns per input cell, i.e. an up-sampling factor below ~2
-        def taps_fit(ni, no):
-            return no <= 6 if ni <= 1 else 2.0 * (no - 1) / (ni - 1) + 2.0 <= 6.0
-        return (widths[0] == widths[1] and widths[0] % 2 == 0 and 0 < widths[2] <= cp and sum(widths) % 4 == 0
-                and h2 > 0 and w2 > 0 and taps_fit(h1, h2) and taps_fit(w1, w2) and ops.scaler_chain_ok(convs, act))
+        # what the segment resize kernels take: an even segment width (out_dim = 112 / 160 give 37 / 53: those run the
+        # conv1 / conv2 / conv3 + cat path below), and an up-sampling factor below ~2 in the backward
+        return (widths[0] == widths[1] and h2 > 0 and w2 > 0
+                and H.bilinear2d_seg_supported(sum(widths), widths[0], cp, (h1, w1), (h2, w2))
+                and ops.scaler_chain_ok(convs, act))
 
     def forward(self, x, out_nhwc=False):
         """x (B, C, H, W).  ``out_nhwc`` returns (B, H', W', C') with the layout change fused into the

@@ -1,0 +1,510 @@
+"""The attention node: dropout mode and mask queue, the shared projection stage, the galerkin / linear, fourier and
+softmax cores, SimpleAttentionFn.
+"""
+from __future__ import annotations
+
+import math
+import os
+from types import SimpleNamespace
+
+import torch
+from torch.autograd import Function
+
+from .. import _hip as H
+from ._handoff import _hint_output_mask, _offer_twin, _take_twin, _wanted_mask
+from .dense import _check_res_is_x
+from .elementwise import _c, _next_salt
+
+
+# ----------------------------------------------------------------------------------- dropout bookkeeping
+# The reference applies F.dropout(p_attn) with the *default* p=0.5, training=True to the attention
+# matrix in train and eval alike (layers.py:700-701, 730-731).  Modes:
+#   "reference": stateless-RNG Bernoulli(0.5) mask, x2 rescale (default, reference-faithful)
+#   "off"      : identity (exact-math parity runs)
+#   "replay"   : multiply by explicit masks queued with push_attention_masks() (mask-replay parity)
+_attn_mode = "reference"
+_attn_masks = []
+
+
+def set_attention_dropout(mode: str):
+    global _attn_mode
+    if mode not in ("reference", "off", "replay"):
+        raise ValueError(mode)
+    _attn_mode = mode
+    _attn_masks.clear()
+
+
+def get_attention_dropout() -> str:
+    return _attn_mode
+
+
+def push_attention_masks(masks):
+    """Queue explicit multiplicative masks (values 0 or 2), consumed one per attention call."""
+    _attn_masks.extend(masks)
+
+
+_plain_tiles = [os.environ.get("GT_PLAIN_TILES", "1") != "0"]          # K', V' head tiles without the LayerNorm affine
+_dkv_ln_fused = [os.environ.get("GT_DKV_LN", "1") != "0"]               # gt_galerkin_dkv_ln vs gt_galerkin_dkv + gt_headnorm_bwd
+_qkvnorm_fused = [True]         # QKV projection + head norm in one launch when the library supports the shape
+
+
+# ----------------------------------------------------------------------------------- attention
+def _save_named(ctx, **tensors):
+    """ctx.save_for_backward by name (tensor or None): the only way a tensor travels from the attention forward to its backward."""
+    ctx.saved_names = tuple(tensors)
+    ctx.save_for_backward(*tensors.values())
+
+
+def _saved(ctx):
+    return SimpleNamespace(**dict(zip(ctx.saved_names, ctx.saved_tensors)))
+
+
+def _project_heads(xc, posc, wq, bqkv, gamma, beta, dims, norm_mask, eps, token_norm, fused_ln):
+    """QKV projection + head norm (+ the token-axis norm of K, V): what every kind shares.  Returns (qkv, stats, out3, tn,
+    plain): the raw projection (None where nothing reads it), the LayerNorm statistics, the head tiles [3, T, h, DP], the
+    token-norm triple (kvn, st_k, st_v) or Nones, and whether the tiles are "plain"."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    T, dev = B * n, xc.device
+    if token_norm:
+        # the projection leaves RAW K, V (+ coordinates) in the tiles: no per-token norm, no affine on its epilogue
+        hn_mask, hn_gamma, hn_beta = 0, None, None
+    else:
+        hn_mask, hn_gamma, hn_beta = norm_mask, gamma, beta
+    qkv = out3 = stats = None
+    # "plain" head tiles: when every consumer of K', V' is one of the fused Galerkin kernels, the tiles keep the
+    # normalised values WITHOUT the LayerNorm affine (the consumers apply gamma / beta), the backward takes xh from the
+    # tiles, and the raw projection has no reader left: it is neither written nor allocated (gt_hip.h: hn_plain)
+    plain = fused_ln and _plain_tiles[0] and H.galerkin_ktv_supported(dk, p)
+    if _qkvnorm_fused[0] and dk in (16, 32, 48, 64) and bqkv is not None and H.get_precision() in H.SPLIT_EXACT:
+        # head norm on the projection's epilogue (GT_EP_HEADNORM): one pass less over [T, 3d], one launch less
+        out3 = torch.empty(3, T, h, DP, dtype=torch.float32, device=dev)
+        stats = torch.empty(2, T, h, 2, dtype=torch.float32, device=dev)
+        if not plain and not token_norm:       # (token_norm: no stream is LayerNormed, nothing reads the raw projection)
+            qkv = torch.empty(T, 3 * d, dtype=torch.float32, device=dev)
+        try:
+            # the raw projection is kept for the LayerNorm backward only: the normalised streams' blocks of qkv
+            H.gemm(xc, wq, qkv, T, 3 * d, d, lda=d, ldb=d, ldc=3 * d, bias=bqkv, weight_b=True,
+                   hn=dict(gamma=hn_gamma, beta=hn_beta, pos=posc, out=out3, stats=stats, h=h, dk=dk, p=p,
+                           norm_mask=hn_mask, eps=eps, skip_raw=7 if plain else (~hn_mask) & 7, plain=plain))
+        except H.GtNotSupported:                          # shapes / alignment the fused kernel does not take
+            out3 = None
+    if out3 is None:
+        plain = False
+        qkv = torch.empty(T, 3 * d, dtype=torch.float32, device=dev)
+        H.gemm(xc, wq, qkv, T, 3 * d, d, lda=d, ldb=d, ldc=3 * d, bias=bqkv, weight_b=True)
+        out3, stats = H.headnorm_fwd(qkv, posc, hn_gamma, hn_beta, T, h, dk, p, hn_mask, eps)
+        if token_norm:
+            qkv = None
+    tn = (None, None, None)
+    if token_norm:
+        # out3[1:] keep the raw tiles for the backward (xh is recomputed from them: a zero weight must work); the
+        # normalised pair goes to its own buffer, which the softmax / contraction chain of the core reads and rewrites
+        kvn = torch.empty(2, T, h, DP, dtype=torch.float32, device=dev)
+        _, st_k = H.token_norm_fwd(out3[1], gamma[0], beta[0], eps, B, n, h, dk, p, out=kvn[0])
+        _, st_v = H.token_norm_fwd(out3[2], gamma[1], beta[1], eps, B, n, h, dk, p, out=kvn[1])
+        tn = (kvn, st_k, st_v)
+    return qkv, stats, out3, tn, plain
+
+
+def _project_heads_bwd(s, dO3, ln, g_in, in_mask, dims, norm_mask, token_norm, hbq, has_res):
+    """The tail of every backward: the gradient tiles dO3 [3, T, h, DP] (or ``ln`` = (d_qkv, dgamma, dbeta) where the core
+    already ran the LayerNorm backward) -> dx (+ its masked twin), d(wqkv), d(bqkv), dgamma, dbeta."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    T, dev = B * n, g_in.device
+    if token_norm:
+        # dK', dV' -> gradients of the raw tiles, in place; the affine gradients in (norm_K, norm_V) order
+        dgamma = torch.empty(2, h, dk, dtype=torch.float32, device=dev)
+        dbeta = torch.empty(2, h, dk, dtype=torch.float32, device=dev)
+        H.token_norm_bwd(s.out3[1], dO3[1], s.gamma[0], s.st_k, B, n, h, dk, p, out=dO3[1], dgamma=dgamma[0], dbeta=dbeta[0])
+        H.token_norm_bwd(s.out3[2], dO3[2], s.gamma[1], s.st_v, B, n, h, dk, p, out=dO3[2], dgamma=dgamma[1], dbeta=dbeta[1])
+        # scatter only: the value columns of the three gradient tiles into d_qkv (no stream is LayerNormed, so the raw
+        # projection is not read; where the forward did not keep one, the gradient tiles stand in for the pointer)
+        dqkv, _, _ = H.headnorm_bwd(dO3, s.qkv if s.qkv is not None else dO3, None, s.stats, T, h, dk, p, 0)
+    elif ln is None:
+        dqkv, dgamma, dbeta = H.headnorm_bwd(dO3, s.qkv, s.gamma, s.stats, T, h, dk, p, norm_mask)
+    else:
+        dqkv, dgamma, dbeta = ln
+    dwqkv = torch.empty(3 * d, d, dtype=torch.float32, device=dev)
+    dbqkv = torch.empty(3 * d, dtype=torch.float32, device=dev) if hbq else None
+    dx = torch.empty(T, d, dtype=torch.float32, device=dev)
+    with H.side_branch(dev, T):     # weight gradient next to the data gradient
+        H.gemm(dqkv, s.xc, dwqkv, 3 * d, d, T, layout_a=1, layout_b=1, lda=3 * d, ldb=d, ldc=d, split_k=0,
+               a_colsum=dbqkv)
+    dxm = torch.empty_like(dx) if in_mask is not None else None
+    # (res is x: its gradient, the unmasked g_in, is folded into dx here and the `res` slot of the backward returns None)
+    H.gemm(dqkv, s.wq, dx, T, d, 3 * d, layout_b=1, lda=3 * d, ldb=d, ldc=d, res=g_in if has_res else None,
+           ldr=d, weight_b=True, c_masked=dxm, ldc_masked=d,
+           c_mask=H.dropout_desc(in_mask[0], in_mask[1], dev) if in_mask else None)
+    if dxm is not None:
+        _offer_twin(dx, dxm, *in_mask)
+    H.join_side(dev)
+    if not norm_mask:
+        dgamma = dbeta = None
+    return dx, dwqkv, dbqkv, dgamma, dbeta
+
+
+def _merged_fc_fwd(att, out, rc, wf, bfc, d_out, dims, sign):
+    """fc over the merged heads, shared by the fourier and softmax cores: out = res + sign * dropout(fc(att)) from the head
+    outputs att [T, h*DP].  Returns wpad [d, h*DP], the fc weight with zero columns under the tiles' padding (saved for
+    _merged_fc_bwd)."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    T, hD = B * n, h * DP
+    wpad = torch.zeros(d, h, DP, dtype=torch.float32, device=out.device)
+    wpad[:, :, :Dr] = wf.reshape(d, h, Dr)
+    wpad = wpad.reshape(d, hD)
+    H.gemm(att, wpad, out, T, d, hD, lda=hD, ldb=hD, ldc=d, bias=bfc, drop=d_out, res=rc, ldr=d, out_scale=sign)
+    return wpad
+
+
+def _merged_fc_bwd(s, g, dims, sign, hbf):
+    """Backward of _merged_fc_fwd from the masked gradient g [T, d], s.att and s.wpad: (datt [T, h*DP], dwfc, dbfc)."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    T, hD, dev = B * n, h * DP, g.device
+    dwpad = torch.empty(d, hD, dtype=torch.float32, device=dev)
+    dbfc = torch.empty(d, dtype=torch.float32, device=dev) if hbf else None
+    H.gemm(g, s.att, dwpad, d, hD, T, layout_a=1, layout_b=1, lda=d, ldb=hD, ldc=hD, split_k=0, alpha=sign,
+           a_colsum=dbfc, a_drop_sign=sign)     # (alpha signs the product, a_drop_sign the column sums)
+    dwfc = dwpad.reshape(d, h, DP)[:, :, :Dr].reshape(d, h * Dr)
+    datt = torch.empty(T, hD, dtype=torch.float32, device=dev)
+    H.gemm(g, s.wpad, datt, T, hD, d, layout_b=1, lda=d, ldb=hD, ldc=hD, alpha=sign)
+    return datt, dwfc, dbfc
+
+
+def _galerkin_fwd(kind, Qp, Kp, Vp, out, rc, wf, bfc, affine, mask, d_attn, d_out, dims, sign):
+    """galerkin / linear core: M = mask .* (K'^T V')/n, out = res + sign * dropout(fc(Q' M)).  ``affine`` = (gamma, beta) for
+    "plain" tiles, else (None, None).  Returns (attn_weight, tensors to save)."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    hD, dev = h * DP, out.device
+    # gt_galerkin_ktv reads the coordinate columns once, from K', for both operands: right for [pos, K], [pos, V]
+    streaming = True
+    if kind == "linear":
+        # Q~ = softmax over the head's columns, K~ = softmax over the tokens, both in place: the backward needs the
+        # softmax outputs only, and the LayerNorm backward of K reads the raw projection, not the tiles
+        H.feature_softmax_fwd(Qp, B * n * h, dk, p, out=Qp)
+        H.token_softmax_fwd(Kp, B, n, h, dk, p, out=Kp)
+        # ... not for K~, whose coordinate columns went through the token softmax: with coordinates the full tiles are
+        # contracted through gt_gemm below
+        streaming = p == 0
+    slabs = H.galerkin_ktv(Kp, Vp, B, n, h, dk, p, gamma=affine[0], beta=affine[1]) if streaming else None
+    if slabs is None:                                       # head sizes the streaming MFMA kernel does not cover
+        slabs = torch.empty(1, B, h, DP, DP, dtype=torch.float32, device=dev)
+        H.gemm(Kp, Vp, slabs, DP, DP, n, layout_a=1, layout_b=1, lda=hD, ldb=hD, ldc=DP, batch=(B, h),
+               a_bs=(n * hD, DP), b_bs=(n * hD, DP), c_bs=(h * DP * DP, DP * DP), split_k=0)
+    Mt, P, Pv = H.galerkin_finalize_fwd(slabs, slabs.shape[0], B * h * DP * DP, B, h, DP, Dr, d, n, mask,
+                                        d_attn, wf, value_rows_of=p)
+    H.gemm(Qp, P, out, n, d, hD, layout_b=1, lda=hD, ldb=d, ldc=d, batch=(B, 1), a_bs=(n * hD, 0),
+           b_bs=(hD * d, 0), c_bs=(n * d, 0), bias=bfc, drop=d_out, res=rc, ldr=d, r_bs=(n * d, 0),
+           out_scale=sign)
+    return Mt[:, :, :Dr, :Dr], dict(wf=wf, Mt=Mt, P=P, Pv=Pv)
+
+
+def _galerkin_bwd(kind, s, g, d_attn, dims, sign, hbf, token_norm, plain, fused_ln):
+    """Backward of _galerkin_fwd from the masked gradient g [T, d].  Returns (dO3, ln, dwfc, dbfc): the gradient tiles, or
+    with ``fused_ln`` ln = (d_qkv, dgamma, dbeta) from gt_galerkin_dkv_ln and dO3 = None."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    T, hD, dev = B * n, h * DP, g.device
+    dbfc = torch.empty(d, dtype=torch.float32, device=dev) if hbf else None
+    # (token_norm: the contractions ran on the normalised pair; out3[1:] are the raw tiles)
+    Qp, (Kp, Vp) = s.out3[0], (s.kvn if token_norm else s.out3[1:])
+    # dP^T[b] = (sign*g*mask1)^T[b] Q'[b]        [B, d, h*DP]
+    dPt = torch.empty(B, d, hD, dtype=torch.float32, device=dev)
+    with H.side_branch(dev, T): # the token-contracted product next to the token-row product below
+        H.gemm(g, Qp, dPt, d, hD, n, layout_a=1, layout_b=1, lda=d, ldb=hD, ldc=hD, batch=(B, 1),
+               a_bs=(n * d, 0), b_bs=(n * hD, 0), c_bs=(d * hD, 0), split_k=0, alpha=sign,
+               a_colsum=dbfc, a_drop_sign=sign)     # + d(fc bias) = column sums of the masked g; a_drop_sign is ITS sign
+    # dQ'[b] = (sign*g*mask1)[b] P[b]^T
+    dO3 = dqkv = None
+    if fused_ln:
+        # only the value columns of dQ' reach d_qkv (the coordinates take no gradient): contract with those rows
+        # of P and write the Q block of d_qkv directly -- one 128-wide tile column instead of h*DP = 144, no
+        # dQ' round trip
+        dqkv = torch.empty(T, 3 * d, dtype=torch.float32, device=dev)
+        H.gemm(g, s.Pv, dqkv, n, d, d, lda=d, ldb=d, ldc=3 * d, batch=(B, 1), a_bs=(n * d, 0),
+               b_bs=(d * d, 0), c_bs=(n * 3 * d, 0), alpha=sign)
+    else:
+        dO3 = torch.empty(3, T, h, DP, dtype=torch.float32, device=dev)
+        H.gemm(g, s.P, dO3[0], n, hD, d, lda=d, ldb=d, ldc=hD, batch=(B, 1), a_bs=(n * d, 0),
+               b_bs=(hD * d, 0), c_bs=(n * hD, 0), alpha=sign)
+    H.join_side(dev)
+    dM, dWs = H.galerkin_finalize_bwd(dPt, s.Mt, s.mask, d_attn, s.wf, B, h, DP, Dr, d, n)
+    dwfc = torch.empty(d, h * Dr, dtype=torch.float32, device=dev)
+    H.slab_reduce(dWs, B, d * h * Dr, d * h * Dr, dwfc)
+    # dK' = V' dM^T ; dV' = K' dM          per (b, head)
+    ln = None
+    if fused_ln:       # ... with the head LayerNorm backward behind them: dK', dV' stay in registers
+        ln = H.galerkin_dkv_ln(Kp, Vp, dM, None, s.qkv, s.gamma, s.stats, B, n, h, dk, p, d_qkv=dqkv,
+                               beta=s.beta if plain else None)
+    elif DP in H.FOURIER_DP:                           # one streaming pass (gt_galerkin_dkv)
+        H.galerkin_dkv(Kp, Vp, dM, dO3[1], dO3[2], B, n, h, DP)
+    else:
+        H.gemm(Vp, dM, dO3[1], n, DP, DP, lda=hD, ldb=DP, ldc=hD, batch=(B, h), a_bs=(n * hD, DP),
+               b_bs=(h * DP * DP, DP * DP), c_bs=(n * hD, DP))
+        H.gemm(Kp, dM, dO3[2], n, DP, DP, layout_b=1, lda=hD, ldb=DP, ldc=hD, batch=(B, h),
+               a_bs=(n * hD, DP), b_bs=(h * DP * DP, DP * DP), c_bs=(n * hD, DP))
+    if kind == "linear":
+        # (the softmax backwards sit between dK' and the LayerNorm backward, so the fused kernel never applies here)
+        # Qp, Kp hold Q~, K~: dQ' = Q~ .* (dQ~ - sum_c Q~ dQ~), dK' = K~ .* (dK~ - sum_t K~ dK~), in place
+        H.feature_softmax_bwd(Qp, dO3[0], T * h, dk, p, out=dO3[0])
+        H.token_softmax_bwd(Kp, dO3[1], B, n, h, dk, p, out=dO3[1])
+    return dO3, ln, dwfc, dbfc
+
+
+def _fourier_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn, d_out, dims, sign, need_w):
+    """fourier core: S = mask .* (Q' K'^T)/sqrt(d_k')/n, out = res + sign * dropout(fc(S V')), on one of three routes: fused
+    fp32, fused two-term fp16 (with the presplit images kept for the backward), or materialised S.  Returns (attn_weight,
+    tensors to save, (flash, f16, block16)): the route, decided once here; the backward follows it."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    T, hD, dev = B * n, h * DP, out.device
+    hd_bs, nn_bs = (n * hD, DP), (h * n * n, n * n)      # batch strides over (sample, head): head tiles, n x n matrices
+    scale = 1.0 / math.sqrt(Dr) / n
+    # fp16 arithmetic active: every width of the fp16 kernel runs on it; otherwise (f32 / bf16 modes) the fp32-MFMA kernel,
+    # which has the same widths behind two entry points (H.fourier_attn picks)
+    flash = (not need_w) and (DP in H.FOURIER_DP + H.FOURIER_DP_WIDE or (DP in H.FOURIER16_DP and H.fourier16_active()))
+    f16 = flash and H.fourier16_active()
+    # fp16 arithmetic: the p = 0.5 score mask is drawn per 4 x 4 block (one hash per block: gt_hip.h), by the fused
+    # kernels and by the materialising path alike
+    block16 = bool(H.fourier16_active() and d_attn is not None and H.fourier16_block_mask(d_attn))
+    S = iq = ik = iv = None
+    if f16:
+        # fused (Q'K'^T * scale .* mask) V': the n x n matrix never reaches HBM.  Two-term fp16 kernels: the head tiles
+        # are split once into fragment-ordered images, kept for the backward
+        iq, ik, iv = H.fourier16_presplit((Qp, Kp, Vp), B, n, h, DP)
+        att = H.fourier16_attn(iq, None, ik, iv, B, n, h, DP, scale, mask, d_attn, False, block16=block16).reshape(T, hD)
+    elif flash:
+        att = H.fourier_attn(Qp, None, Kp, Vp, B, n, h, DP, scale, mask, d_attn, False).reshape(T, hD)
+    else:
+        S = torch.empty(B, h, n, n, dtype=torch.float32, device=dev)
+        H.gemm(Qp, Kp, S, n, n, DP, lda=hD, ldb=hD, ldc=n, batch=(B, h), a_bs=hd_bs, b_bs=hd_bs, c_bs=nn_bs, alpha=scale,
+               drop=None if block16 else d_attn, aux_op=H.AUX_MUL if mask is not None else H.AUX_NONE, aux=mask, ldaux=n,
+               aux_bs=nn_bs)
+        if block16:
+            H.dropout_block16(S, B * h, n, d_attn)
+        att = torch.empty(T, hD, dtype=torch.float32, device=dev)
+        H.gemm(S, Vp, att, n, DP, n, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs, b_bs=hd_bs, c_bs=hd_bs)
+    wpad = _merged_fc_fwd(att, out, rc, wf, bfc, d_out, dims, sign)
+    attn_w = S if S is not None else torch.empty(0, device=dev)
+    return attn_w, dict(wpad=wpad, S=S, att=att, iq=iq, ik=ik, iv=iv), (flash, f16, block16)
+
+
+def _fourier_bwd(s, g, d_attn, dims, sign, hbf, flash, f16, block16):
+    """Backward of _fourier_fwd on the route it took.  Returns (dO3, dwfc, dbfc)."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    T, hD, dev = B * n, h * DP, g.device
+    hd_bs, nn_bs = (n * hD, DP), (h * n * n, n * n)      # batch strides over (sample, head): head tiles, n x n matrices
+    dO3 = torch.empty(3, T, h, DP, dtype=torch.float32, device=dev)
+    Qp, Kp, Vp = s.out3[0], s.out3[1], s.out3[2]
+    scale = 1.0 / math.sqrt(Dr) / n
+    datt, dwfc, dbfc = _merged_fc_bwd(s, g, dims, sign, hbf)
+    datt3 = datt.reshape(T, h, DP)
+    if f16:       # fused passes: dQ' = (dO V'^T .* m) K' ;  dV' = (S .* m)^T dO, dK' = (dO V'^T .* m)^T Q'
+        (ido,) = H.fourier16_presplit((datt3,), B, n, h, DP)
+        H.fourier16_attn(ido, None, s.iv, s.ik, B, n, h, DP, scale, s.mask, d_attn, False, O1=dO3[0], block16=block16)
+        H.fourier16_attn(s.ik, s.iv, s.iq, ido, B, n, h, DP, scale, s.mask, d_attn, True, O1=dO3[2], O2=dO3[1],
+                         block16=block16)
+    elif flash:
+        H.fourier_attn(datt3, None, Vp, Kp, B, n, h, DP, scale, s.mask, d_attn, False, O1=dO3[0])
+        H.fourier_attn(Kp, Vp, Qp, datt3, B, n, h, DP, scale, s.mask, d_attn, True, O1=dO3[2], O2=dO3[1])
+    else:
+        dS = torch.empty(B, h, n, n, dtype=torch.float32, device=dev)
+        H.gemm(datt, Vp, dS, n, n, DP, lda=hD, ldb=hD, ldc=n, batch=(B, h), a_bs=hd_bs, b_bs=hd_bs, c_bs=nn_bs, alpha=scale,
+               drop=None if block16 else d_attn, aux_op=H.AUX_MUL if s.mask is not None else H.AUX_NONE, aux=s.mask, ldaux=n,
+               aux_bs=nn_bs)
+        if block16:
+            H.dropout_block16(dS, B * h, n, d_attn)
+        # dV' = S^T datt ; dQ' = dS K' ; dK' = dS^T Q'
+        H.gemm(s.S, datt, dO3[2], n, DP, n, layout_a=1, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs,
+               b_bs=hd_bs, c_bs=hd_bs)
+        H.gemm(dS, Kp, dO3[0], n, DP, n, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs, b_bs=hd_bs, c_bs=hd_bs)
+        H.gemm(dS, Qp, dO3[1], n, DP, n, layout_a=1, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs,
+               b_bs=hd_bs, c_bs=hd_bs)
+    return dO3, dwfc, dbfc
+
+
+def _softmax_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn, d_out, dims, sign, need_w):
+    """softmax core: P = softmax(Q' K'^T / sqrt(d_k')), out = res + sign * dropout(fc((P .* mask) V')), fused (gt_softmax_attn_*:
+    no n x n matrix in HBM; gt_softmax_attn_wide_* at DP 68 / 100) or, when the weights are wanted, materialised (gt_gemm +
+    gt_row_softmax_*).  The attention runs in fp32 on both routes in every precision mode; the fc product follows
+    set_precision.  Returns (attn_weight = P .* mask, tensors to save, flash): the route, decided once here; the backward
+    follows it."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    T, hD, dev = B * n, h * DP, out.device
+    hd_bs, nn_bs = (n * hD, DP), (h * n * n, n * n)      # batch strides over (sample, head): head tiles, n x n matrices
+    scale = 1.0 / math.sqrt(Dr)
+    flash = not need_w
+    P = Pm = L = None
+    if flash:
+        att, L = H.softmax_attn_fwd(Qp, Kp, Vp, B, n, h, DP, scale, mask, d_attn)
+        att = att.reshape(T, hD)
+    else:
+        P = torch.empty(B, h, n, n, dtype=torch.float32, device=dev)
+        H.gemm(Qp, Kp, P, n, n, DP, lda=hD, ldb=hD, ldc=n, batch=(B, h), a_bs=hd_bs, b_bs=hd_bs, c_bs=nn_bs, alpha=scale,
+               precision="f32")
+        P, Pm = H.row_softmax_fwd(P, B * h * n, n, mask, d_attn, P=P)      # in place; Pm is P without mask and dropout
+        att = torch.empty(T, hD, dtype=torch.float32, device=dev)
+        H.gemm(Pm, Vp, att, n, DP, n, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs, b_bs=hd_bs, c_bs=hd_bs,
+               precision="f32")
+    wpad = _merged_fc_fwd(att, out, rc, wf, bfc, d_out, dims, sign)
+    attn_w = Pm if Pm is not None else torch.empty(0, device=dev)
+    return attn_w, dict(wpad=wpad, att=att, L=L, P=P, Pm=Pm), flash
+
+
+def _softmax_bwd(s, g, d_attn, dims, sign, hbf, flash):
+    """Backward of _softmax_fwd on the route it took.  Returns (dO3, dwfc, dbfc)."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    T, hD, dev = B * n, h * DP, g.device
+    hd_bs, nn_bs = (n * hD, DP), (h * n * n, n * n)      # batch strides over (sample, head): head tiles, n x n matrices
+    dO3 = torch.empty(3, T, h, DP, dtype=torch.float32, device=dev)
+    Qp, Kp, Vp = s.out3[0], s.out3[1], s.out3[2]
+    scale = 1.0 / math.sqrt(Dr)
+    datt, dwfc, dbfc = _merged_fc_bwd(s, g, dims, sign, hbf)
+    if flash:     # dQ' (and D), then dK', dV': P = exp(S - L) recomputed tile by tile
+        H.softmax_attn_bwd(datt.reshape(T, h, DP), s.att.reshape(T, h, DP), Qp, Kp, Vp, s.L, B, n, h, DP, scale, s.mask,
+                           d_attn, dQ=dO3[0], dK=dO3[1], dV=dO3[2])
+    else:
+        dS = torch.empty(B, h, n, n, dtype=torch.float32, device=dev)
+        H.gemm(datt, Vp, dS, n, n, DP, lda=hD, ldb=hD, ldc=n, batch=(B, h), a_bs=hd_bs, b_bs=hd_bs,
+               c_bs=nn_bs, precision="f32")                                # dPm = dO V'^T
+        H.row_softmax_bwd(s.P, dS, B * h * n, n, s.mask, d_attn, dS=dS)     # dS = P .* (m .* dPm - sum P m dPm), in place
+        # dV' = Pm^T datt ; dQ' = dS K' / sqrt(d_k') ; dK' = dS^T Q' / sqrt(d_k')
+        H.gemm(s.Pm, datt, dO3[2], n, DP, n, layout_a=1, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs,
+               b_bs=hd_bs, c_bs=hd_bs, precision="f32")
+        H.gemm(dS, Kp, dO3[0], n, DP, n, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs,
+               b_bs=hd_bs, c_bs=hd_bs, alpha=scale, precision="f32")
+        H.gemm(dS, Qp, dO3[1], n, DP, n, layout_a=1, layout_b=1, lda=n, ldb=hD, ldc=hD, batch=(B, h), a_bs=nn_bs,
+               b_bs=hd_bs, c_bs=hd_bs, alpha=scale, precision="f32")
+    return dO3, dwfc, dbfc
+
+
+class SimpleAttentionFn(Function):
+    """out = res + sign * dropout1( fc( merge_heads( attention(Q', K', V') ) ) ).
+
+    galerkin: per-head LN on K,V; M = mask .* (K'^T V')/n; heads: Q' M      (layers.py:708-734)
+    linear  : the same on Q~ = softmax(Q', dim=-1), K~ = softmax(K', dim=-2)  (layers.py:719-722; 'global' too)
+    fourier : per-head LN on Q,K; S = mask .* (Q' K'^T)/sqrt(d_k')/n; heads: S V' (layers.py:672-705)
+    softmax : per-head LN on Q,K; P = softmax(Q' K'^T/sqrt(d_k')); heads: (mask .* P) V'  (layers.py:691-703)
+    with X' = [pos, X] per head (layers.py:869-874) and fc over the merged heads (layers.py:894-897).
+    token_norm (norm_type='instance', galerkin / linear): K, V are normalised over the TOKENS per (sample, head, channel)
+    instead (layers.py:842-854): the projection writes raw tiles, gt_token_norm_fwd normalises their value columns.
+    Also returns the attention matrix (``attn_weight``), detached.
+
+    One autograd node in two stages.  forward: _project_heads (QKV projection, head norm, token norm; shared), then the core
+    of the kind, _galerkin_fwd (galerkin, linear), _fourier_fwd or _softmax_fwd, which ends in the fc product that writes
+    ``out`` (fourier and softmax share that stage: _merged_fc_fwd / _merged_fc_bwd; galerkin folds fc into P).  backward:
+    _galerkin_bwd / _fourier_bwd / _softmax_bwd, then _project_heads_bwd.  Forward to backward: the tensors go by name through
+    _save_named / _saved; ctx.cfg, ctx.dims, ctx.salt, ctx.has (bqkv, bfc, res given), ctx.xshape and ctx.in_mask carry the
+    call; ctx.plain, ctx.fused_ln and, for fourier, ctx.flash, ctx.f16, ctx.block16 (softmax: ctx.flash) record every route the forward chose.
+    The backward follows them and consults no module-level switch."""
+
+    @staticmethod
+    def forward(ctx, x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, cfg, mask):
+        (kind, h, norm_mask, eps, sign, p_attn, p_out, need_w, token_norm) = cfg
+        if kind not in ("galerkin", "linear", "fourier", "softmax"):
+            raise ValueError(f"simple_attention: kind={kind!r}")
+        if token_norm and (kind in ("fourier", "softmax") or norm_mask != 0b110 or gamma is None or beta is None):
+            raise ValueError("simple_attention: token_norm is the K, V norm of the galerkin / linear kinds")
+        H.need_f32_cuda(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, mask)
+        B, n, d = x.shape
+        dk = d // h
+        p = 0 if pos is None else pos.shape[-1]
+        Dr, DP = dk + p, H.round4(dk + p)
+        T = B * n
+        dev = x.device
+        if kind == "linear" and not H.linattn_supported(dk, p):
+            raise H.GtNotSupported(f"linear attention: head size d_k={dk}, pos_dim={p} has no softmax kernel")
+        if kind == "softmax" and DP not in H.SOFTMAX_DP + H.SOFTMAX_DP_WIDE:
+            raise H.GtNotSupported(f"softmax attention: head tile width round4(d_k + pos_dim) = {DP} has no kernel "
+                                   f"(supported: {H.SOFTMAX_DP} and {H.SOFTMAX_DP_WIDE}, i.e. d_k in (16, 32, 48, 64, 96) "
+                                   f"with 1..4 coordinate columns)")
+        if token_norm:
+            if n < 2:       # nn.InstanceNorm1d: "Expected more than 1 spatial element when training"
+                raise ValueError(f"norm_type='instance' needs more than 1 token per sample to normalise over (got n={n})")
+            if not H.linattn_supported(dk, p):
+                raise H.GtNotSupported(f"norm_type='instance': head size d_k={dk}, pos_dim={p} has no token-norm kernel")
+        # the Galerkin backward with the head LayerNorm backward fused in (gt_galerkin_dkv_ln); not for linear, whose softmax
+        # backwards sit between dK' and the LayerNorm backward
+        fused_ln = (kind == "galerkin" and not token_norm and _dkv_ln_fused[0]
+                    and H.galerkin_dkv_ln_supported(dk, p, norm_mask))
+        dims = (B, n, d, h, dk, p, Dr, DP)
+        xc = _c(x).reshape(T, d)
+        posc = None if pos is None else _c(pos).reshape(T, p)
+        wq, wf = _c(wqkv), _c(wfc)
+        salt = _next_salt(4)
+        qkv, stats, out3, (kvn, st_k, st_v), plain = _project_heads(xc, posc, wq, bqkv, gamma, beta, dims, norm_mask, eps,
+                                                                    token_norm, fused_ln)
+        Qp, Kp, Vp = (out3[0], kvn[0], kvn[1]) if token_norm else (out3[0], out3[1], out3[2])
+        out = torch.empty(T, d, dtype=torch.float32, device=dev)
+        rc = None if res is None else _c(res).reshape(T, d)
+        d_attn = H.dropout_desc(p_attn, salt, dev) if (p_attn > 0 and mask is None) else None
+        d_out = H.dropout_desc(p_out, salt + 1, dev) if p_out > 0 else None
+        if kind in ("galerkin", "linear"):
+            attn_w, core = _galerkin_fwd(kind, Qp, Kp, Vp, out, rc, wf, bfc, (gamma, beta) if plain else (None, None), mask,
+                                         d_attn, d_out, dims, sign)
+        elif kind == "softmax":
+            attn_w, core, ctx.flash = _softmax_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn, d_out, dims, sign, need_w)
+        else:
+            attn_w, core, (ctx.flash, ctx.f16, ctx.block16) = _fourier_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn,
+                                                                           d_out, dims, sign, need_w)
+        _save_named(ctx, xc=xc, wq=wq, gamma=gamma, beta=beta, qkv=qkv, stats=stats, out3=out3, kvn=kvn, st_k=st_k,
+                    st_v=st_v, mask=mask, **core)
+        ctx.plain, ctx.fused_ln = plain, fused_ln
+        ctx.cfg, ctx.dims, ctx.salt, ctx.xshape = cfg, dims, salt, x.shape
+        ctx.has = (bqkv is not None, bfc is not None, res is not None)
+        ctx.in_mask = _wanted_mask(xc)
+        _hint_output_mask(out, p_out, salt + 1)
+        attn_w = attn_w.detach()
+        ctx.mark_non_differentiable(attn_w)
+        return out.reshape(x.shape), attn_w
+
+    @staticmethod
+    def backward(ctx, gy, _gw):
+        (kind, h, norm_mask, eps, sign, p_attn, p_out, need_w, token_norm) = ctx.cfg
+        B, n, d = ctx.dims[:3]
+        hbq, hbf, has_res = ctx.has
+        salt, dev = ctx.salt, gy.device
+        s = _saved(ctx)
+        g = _c(gy).reshape(B * n, d)
+        g_in = g                                             # unmasked: what flows to the residual branch
+        if p_out > 0:                                        # mask once, not in every consumer's operand loader
+            gmk = _take_twin(g, p_out, salt + 1)             # ... and not at all when the consumer of `out` wrote the copy
+            g = gmk if gmk is not None else H.dropout_apply(g, H.dropout_desc(p_out, salt + 1, dev))
+        d_attn = H.dropout_desc(p_attn, salt, dev) if (p_attn > 0 and s.mask is None) else None
+        ln = None
+        if kind in ("galerkin", "linear"):
+            dO3, ln, dwfc, dbfc = _galerkin_bwd(kind, s, g, d_attn, ctx.dims, sign, hbf, token_norm, ctx.plain,
+                                                ctx.fused_ln)
+        elif kind == "softmax":
+            dO3, dwfc, dbfc = _softmax_bwd(s, g, d_attn, ctx.dims, sign, hbf, ctx.flash)
+        else:
+            dO3, dwfc, dbfc = _fourier_bwd(s, g, d_attn, ctx.dims, sign, hbf, ctx.flash, ctx.f16, ctx.block16)
+        dx, dwqkv, dbqkv, dgamma, dbeta = _project_heads_bwd(s, dO3, ln, g_in, ctx.in_mask, ctx.dims, norm_mask, token_norm,
+                                                             hbq, has_res)
+        return (dx.reshape(ctx.xshape), None, dwqkv, dbqkv, dgamma, dbeta, dwfc, dbfc, None, None, None)
+
+
+def simple_attention(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, *, kind: str, n_head: int, norm_mask: int,
+                     eps: float, res=None, sign: float = 1.0, p_out: float = 0.0, need_weights: bool = True,
+                     token_norm: bool = False):
+    """Self-attention block; ``res`` must be ``x`` (or None).  Returns (out, attn_weight).  For the Fourier and softmax
+    types ``need_weights=False`` selects the fused kernel that never materialises the n x n matrix
+    (attn_weight is then None); the Galerkin matrix is small and always returned.  ``token_norm`` (galerkin / linear with
+    norm_mask = K, V): gamma / beta are the affine of the token-axis norm (norm_type='instance') instead of the LayerNorm's."""
+    _check_res_is_x(res, x, "simple_attention")
+    mode = _attn_mode
+    mask, p_attn = None, 0.0
+    if mode == "reference":
+        p_attn = 0.5
+    elif mode == "replay":
+        if not _attn_masks:
+            raise RuntimeError("attention dropout mode 'replay' but no mask queued")
+        m = _attn_masks.pop(0).to(device=x.device, dtype=torch.float32)
+        if kind in ("galerkin", "linear"):
+            Dr = m.shape[-1]
+            DP = H.round4(Dr)
+            mask = torch.zeros(*m.shape[:2], DP, DP, dtype=torch.float32, device=x.device)
+            mask[..., :Dr, :Dr] = m
+        else:
+            mask = _c(m)
+    cfg = (kind, int(n_head), int(norm_mask), float(eps), float(sign), float(p_attn), float(p_out),
+           bool(need_weights), bool(token_norm))
+    out, w = SimpleAttentionFn.apply(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, cfg, mask)
+    return out, (w if w.numel() else None)

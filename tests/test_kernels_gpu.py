@@ -335,11 +335,13 @@ def test_ops_refuse_cpu_tensors(H):
 @pytest.mark.parametrize("in_nhwc,out_nhwc", [(False, False), (False, True), (True, False), (True, True)])
 @pytest.mark.parametrize("B,C,ni,no,act", [(2, 128, 43, 77, 0), (2, 128, 78, 43, 1), (1, 36, 141, 78, 1),
                                            (3, 8, 5, 33, 0), (1, 4, 7, 1, 0), (2, 68, 1, 6, 0),
-                                           (1, 12, 34, 34, 1)])
+                                           (1, 12, 34, 34, 1), (1, 8, 4, 30, 1), (1, 4, 2, 9, 1)])
 def test_bilinear_resize_layouts(H, gpu_device, in_nhwc, out_nhwc, B, C, ni, no, act):
     """gt_bilinear2d_fwd/bwd against F.interpolate(mode='bilinear', align_corners=True) (+ReLU) on the
     CPU in fp32 (the reference's arithmetic: source index and weights are fp32 there too), every layout
-    combination, up- and down-sampling, degenerate sizes."""
+    combination, up- and down-sampling, degenerate sizes.  The last two: more contributing outputs per input cell than
+    the backward's register tables hold (RS_MAXT = 6), with the ReLU gate -- on both axes (4 -> 30, 7 -> 28), and on the
+    rows only (2 -> 9) while the columns (5 -> 7) fit."""
     import torch.nn.functional as F
     nj, nq = ni + 3, max(1, no - 2)                     # non-square: H = ni -> no, W = nj -> nq
     x = rnd(B, C, ni, nj, dev="cpu", seed=1).requires_grad_(True)
@@ -360,6 +362,25 @@ def test_bilinear_resize_layouts(H, gpu_device, in_nhwc, out_nhwc, B, C, ni, no,
     assert rel_l2(dgot, x.grad) < KTOL
     dx2 = H.bilinear2d_bwd(g, out if act else None, (ni, nj), in_nhwc, out_nhwc, act)
     assert torch.equal(dx, dx2)                         # gather formulation: bitwise deterministic
+
+
+@pytest.mark.parametrize("rp", [0, 1, 2, 3])
+def test_bilinear_resize_affine(H, gpu_device, rp):
+    """gt_bilinear2d_fwd_affine, channels-last on both sides, against interpolate + bias + rp_a @ rp_b^T on the CPU in fp32.
+    The kernel carries rp = 1 and 2 in registers; rp = 3 is the only route into the general loop (resize_affine)."""
+    import torch.nn.functional as F
+    B, C, Hi, Wi, Ho, Wo = 2, 8, 5, 6, 9, 11
+    x, bias = rnd(B, C, Hi, Wi, dev="cpu", seed=5), rnd(C, dev="cpu", seed=6)
+    ref = F.interpolate(x, size=(Ho, Wo), mode="bilinear", align_corners=True).permute(0, 2, 3, 1) + bias
+    rp_a = rp_b = None
+    if rp:
+        rp_a, rp_b = rnd(B, Ho, Wo, rp, dev="cpu", seed=7), rnd(C, rp, dev="cpu", seed=8)
+        ref = ref + rp_a @ rp_b.t()
+        rp_a, rp_b = rp_a.to(gpu_device), rp_b.to(gpu_device)
+    out = H.bilinear2d_fwd(x.permute(0, 2, 3, 1).contiguous().to(gpu_device), (Ho, Wo), True, True, H.ACT_NONE,
+                           bias=bias.to(gpu_device), rp_a=rp_a, rp_b=rp_b, rp_ldb=rp)
+    assert tuple(out.shape) == (B, Ho, Wo, C)
+    assert rel_l2(out, ref) < KTOL
 
 
 def test_bilinear_resize_autograd_scale_factor(H, gpu_device):

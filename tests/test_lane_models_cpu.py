@@ -768,7 +768,7 @@ def test_x3w_chunk_major_block_order(tiles, n_split):
 
 @pytest.mark.parametrize("Cout,npx", [(128, 70), (64, 33), (16, 5)])
 def test_conv0_decision_bits_layout(Cout, npx):
-    """relu_bits of the fused conv0 + resize (gt_resize.hip): the forward thread of (pixel e, channel block bc of 16) writes
+    """relu_bits of the fused conv0 + resize (gt_convresize.hip): the forward thread of (pixel e, channel block bc of 16) writes
     ONE 64-bit word [b][bc][e] with nibble j = channel 16 bc + j; the backward thread of (pixel e, channel group c0 of 8) reads
     the same word, takes its low or high half by c0 & 8, and tests bit 4 j + t for channel c0 + j, source pixel t."""
     rng = np.random.default_rng(Cout + npx)

@@ -114,6 +114,12 @@ _PROTOS = {
     "gt_token_norm_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 2 + [C.c_int32] * 5
                           + [C.c_void_p, C.c_int64, C.c_void_p]),
     "gt_token_norm_bwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 5 + [C.c_void_p, C.c_int64, C.c_void_p]),
+    "gt_batchnorm_ws_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
+    "gt_batchnorm_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 2 + [C.c_float, C.c_int32]
+                         + [C.c_void_p] * 3 + [C.c_int64, C.c_int32] + [C.c_void_p, C.c_int64, C.c_void_p]),
+    "gt_batchnorm_bwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int64] + [C.c_int32] * 3 + [C.c_void_p, C.c_float,
+                                                                                     C.POINTER(GtDropout)]
+                         + [C.c_void_p, C.c_int64, C.c_void_p]),
     "gt_fourier_attn": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.POINTER(GtDropout),
                                                                 C.c_int32, C.c_void_p]),
     "gt_fourier_attn_wide": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.POINTER(GtDropout),
@@ -1263,6 +1269,47 @@ def token_norm_bwd(X: torch.Tensor, dY: torch.Tensor, gamma: torch.Tensor, stats
     ws = workspace(X.device, max(16, lib().gt_token_norm_ws_bytes(B, n, h, dk, p)))
     _launch("gt_token_norm_bwd", X, dY, gamma, stats, out, dgamma, dbeta, B, n, h, dk, p, ws=ws,
             nbytes=20.0 * B * n * h * round4(dk + p), shape=(B, n, h, dk, p))
+    return out, dgamma, dbeta
+
+
+def batchnorm_fwd(hid: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
+                  running_mean: Optional[torch.Tensor], running_var: Optional[torch.Tensor], momentum: float, training: bool,
+                  out: Optional[torch.Tensor] = None):
+    """BatchNorm1d over the rows of the dense hidden matrix hid [T, f] (one mean / biased variance per column); gamma, beta
+    and the running buffers [f].  training: batch statistics, the running buffers updated in place (when given); else the
+    running buffers are the statistics.  Returns (z, stats [f, 2] = (mean, rstd), bvar [f]); ``out=hid`` runs in place."""
+    need_f32_cuda(hid, gamma, beta, running_mean, running_var, out)
+    T, f = hid.shape
+    if not hid.is_contiguous() or (out is not None and not out.is_contiguous()):
+        raise ValueError("batchnorm_fwd: hid / out must be contiguous")
+    out = torch.empty_like(hid) if out is None else out
+    stats = torch.empty(f, 2, dtype=torch.float32, device=hid.device)
+    bvar = torch.empty(f, dtype=torch.float32, device=hid.device)
+    ws = workspace(hid.device, max(16, lib().gt_batchnorm_ws_bytes(T, f)))
+    _launch("gt_batchnorm_fwd", hid, gamma, beta, float(eps), running_mean, running_var, float(momentum), int(bool(training)),
+            out, stats, bvar, T, f, ws=ws, nbytes=(12.0 if training else 8.0) * T * f, shape=(T, f, int(bool(training))))
+    return out, stats, bvar
+
+
+def batchnorm_bwd(hid: torch.Tensor, dz: torch.Tensor, gamma: torch.Tensor, stats: torch.Tensor, training: bool,
+                  gate=(AUX_NONE, None, 1.0, None), out: Optional[torch.Tensor] = None):
+    """Backward of batchnorm_fwd from the RAW hid and the forward's stats, with the backward of what sits in front of the
+    norm on the store.  gate = (op, aux, scale, drop): (AUX_NONE, None, 1, None), (AUX_GT0, None, 1 / (1 - p_h), None) --
+    ReLU, decided on hid itself -- or (AUX_DSILU, pre, 1, GtDropout or None).  Returns (gh, dgamma [f], dbeta [f]);
+    ``out=dz`` runs in place."""
+    op, aux, scale, drop = gate
+    need_f32_cuda(hid, dz, gamma, stats, aux, out)
+    T, f = hid.shape
+    if not (hid.is_contiguous() and dz.is_contiguous() and (aux is None or aux.is_contiguous())
+            and (out is None or out.is_contiguous())):
+        raise ValueError("batchnorm_bwd: hid / dz / aux / out must be contiguous")
+    out = torch.empty_like(dz) if out is None else out
+    dgamma = torch.empty(f, dtype=torch.float32, device=hid.device)
+    dbeta = torch.empty(f, dtype=torch.float32, device=hid.device)
+    ws = workspace(hid.device, max(16, lib().gt_batchnorm_ws_bytes(T, f)))
+    _launch("gt_batchnorm_bwd", hid, dz, gamma, stats, out, dgamma, dbeta, T, f, int(bool(training)), int(op), aux,
+            float(scale), drop, ws=ws, nbytes=(20.0 + (4.0 if op == AUX_DSILU else 0.0)) * T * f,
+            shape=(T, f, int(bool(training)), int(op)))
     return out, dgamma, dbeta
 
 

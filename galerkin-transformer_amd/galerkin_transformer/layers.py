@@ -469,7 +469,16 @@ class SimpleAttention(nn.Module):
 
 
 class FeedForward(nn.Module):
-    """lr1 -> act -> dropout -> lr2 (layers.py:954-987); one fused HIP operator."""
+    """lr1 -> act -> dropout -> [BatchNorm1d] -> lr2 (layers.py:954-987); one fused HIP operator.
+
+    batch_norm=True puts nn.BatchNorm1d(dim_feedforward) (the reference's `bn`, same state_dict keys) between the hidden
+    dropout and lr2: one mean and one biased variance per hidden channel over all B n token rows, on the gt_batchnorm_*
+    kernels (ops.feed_forward_bn).  In training mode the batch statistics are used and `running_mean`, `running_var` and
+    `num_batches_tracked` are updated on the device; in eval mode the running buffers are the statistics.  Under
+    data-parallel training every rank keeps its own statistics and buffers (torch's behaviour without SyncBatchNorm).
+    Not implemented, and raising NotImplementedError: activation='gelu' together with batch_norm, a `bn` changed to
+    momentum=None, affine=False or track_running_stats=False (none reachable from this constructor), and a hidden width
+    that is no multiple of 4."""
 
     def __init__(self, in_dim=256, dim_feedforward: int = 1024, out_dim=None, batch_norm=False,
                  activation="relu", dropout=0.1):
@@ -488,10 +497,29 @@ class FeedForward(nn.Module):
         self.lr2 = nn.Linear(dim_feedforward, out_dim)
         self.dropout = nn.Dropout(dropout)
 
+    def _fused_forward_bn(self, x, residual, p_h, p_out):
+        bn = self.bn
+        if bn.momentum is None or not bn.affine or not bn.track_running_stats:
+            # a cumulative average (momentum=None) needs the step counter on the host; the other two have no kernel
+            raise NotImplementedError("batch_norm=True on the HIP path needs BatchNorm1d with a momentum, affine=True and "
+                                      "track_running_stats=True")
+        if isinstance(self.activation, nn.GELU):
+            raise NotImplementedError("batch_norm=True with activation='gelu' is outside the HIP hot path")
+        try:
+            out = ops.feed_forward_bn(x, self.lr1.weight, self.lr1.bias, self.lr2.weight, self.lr2.bias, bn.weight, bn.bias,
+                                      bn.running_mean, bn.running_var, res=residual, act=_act_name(self.activation),
+                                      p_h=p_h, p_out=p_out, eps=bn.eps, momentum=bn.momentum, training=bn.training)
+        except H.GtNotSupported as e:
+            raise NotImplementedError(f"batch_norm=True: no HIP kernel for dim_feedforward={self.lr1.out_features} "
+                                      f"(a multiple of 4 is needed): {e}") from e
+        if bn.training:
+            bn.num_batches_tracked.add_(1)      # on the device: no host read-back, capturable in a HIP graph
+        return out
+
     def fused_forward(self, x, residual=None, p_out=0.0):
-        if self.batch_norm:
-            raise NotImplementedError("batch_norm=True is outside the HIP hot path (False in every config)")
         p_h = self.dropout.p if self.training else 0.0
+        if self.batch_norm:
+            return self._fused_forward_bn(x, residual, p_h, p_out)
         if isinstance(self.activation, nn.GELU):
             # activation='gelu' (reference layers.py:968; no config selects it): the two GEMMs with the erf GELU and its
             # dropout as one elementwise pass between them -- the GEMM epilogues carry relu / silu only

@@ -29,7 +29,10 @@ ADDITIONAL_ATTR = ['normalizer', 'raw_laplacian', 'return_latent', 'residual_typ
 
 
 class SimpleTransformerEncoderLayer(nn.Module):
-    """x <- x +/- drop(attn(x)); [LN]; x <- x + drop(ff(x)); [LN]      (reference model.py:33-140)."""
+    """x <- x +/- drop(attn(x)); [LN]; x <- x + drop(ff(x)); [LN]      (reference model.py:33-140).
+
+    batch_norm=True gives the FeedForward an nn.BatchNorm1d(dim_feedforward) behind its hidden dropout (FeedForward's
+    docstring: batch statistics and running buffers per rank, relu / silu only)."""
 
     def __init__(self, d_model=96, pos_dim=1, n_head=2, dim_feedforward=512, attention_type='fourier',
                  pos_emb=False, layer_norm=True, attn_norm=None, norm_type='layer', norm_eps=None,

@@ -13,7 +13,7 @@ One module per operator family; this file only re-exports (every name is the obj
                  one statement of the size-or-scale-factor rule
 ``conv``         conv0 + resize, the wide channels-last 3x3 convolution, the chain of three narrow ones; their filter
                  layouts, weight-gradient route, library fallback, eligibility functions and switches
-``dense``        ``packed_params``, Linear, the regression head, FeedForward
+``dense``        ``packed_params``, Linear, the regression head, FeedForward, FeedForward with BatchNorm1d
 ``attention``    the attention-dropout mode and mask queue, ``SimpleAttentionFn`` with its projection stage and cores
 """
 from ._handoff import (_fold_masks, _fold_seq, _gate_depth, _gate_fold, _hint_output_mask, _mask_hints,  # noqa: F401
@@ -25,8 +25,8 @@ from .conv import (Conv3x3NhwcFn, Conv3x3ResizeFn, ScalerConvChainFn, _conv_impl
                    _conv_wgrad, _conv_wgrad_planes, _crb_bits, _gather_cache, _gathered,
                    _pad_filter, _plain_conv3x3, _scaler_chain, _scaler_wgrad_hip, conv3x3_nhwc, conv3x3_nhwc_implicit,
                    conv3x3_nhwc_ok, conv3x3_resize, scaler_chain_ok, scaler_conv_chain)
-from .dense import (FeedForwardFn, LinearFn, MlpHeadFn, _check_res_is_x, _ffn_bwd_fused, feed_forward,  # noqa: F401
-                    linear, mlp_head, packed_params)
+from .dense import (FeedForwardBNFn, FeedForwardFn, LinearFn, MlpHeadFn, _check_res_is_x, _ffn_bwd_fused,  # noqa: F401
+                    feed_forward, feed_forward_bn, linear, mlp_head, packed_params)
 from .elementwise import (DropActFn, DropoutFn, LayerNormFn, _c, _next_salt, drop_act, dropout,  # noqa: F401
                           layer_norm)
 from .resize import (ResizeFn, ResizeSegFn, UpsampleFcFn, bilinear_resize, bilinear_resize_seg, out_size,  # noqa: F401

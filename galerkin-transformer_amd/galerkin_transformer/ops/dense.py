@@ -314,3 +314,99 @@ def feed_forward(x, w1, b1, w2, b2, res=None, act="relu", p_h=0.0, p_out=0.0):
     """res must be x itself (or None): the fused backward folds d(res) into d(x)."""
     _check_res_is_x(res, x, "feed_forward")
     return FeedForwardFn.apply(x, w1, b1, w2, b2, res, H.ACT_CODE[act], float(p_h), float(p_out))
+
+
+class FeedForwardBNFn(Function):
+    """out = res + dropout2(lr2(BatchNorm1d(dropout_h(act(lr1(x))))))   (layers.py:979-987 with batch_norm=True).
+
+    The norm keeps one mean and one biased variance per hidden channel over all T = B n token rows and sits BEHIND the
+    hidden dropout, so its statistics see the dropped, rescaled values.  training: batch statistics, running_mean /
+    running_var updated in place; else the running buffers are the statistics and the backward has no mean terms.  The two
+    products are FeedForwardFn's unfused pair; between them gt_batchnorm_fwd writes z next to hid (the backward needs both:
+    dW2 contracts z, the norm's backward recomputes xh and the ReLU gate from hid)."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, running_mean, running_var, res, act: int, p_h: float, p_out: float,
+                eps: float, momentum: float, training: bool):
+        H.need_f32_cuda(x, w1, b1, w2, b2, gamma, beta, running_mean, running_var, res)
+        if act not in (H.ACT_RELU, H.ACT_SILU):
+            raise NotImplementedError("FeedForward HIP path with batch_norm implements relu and silu")
+        d, f, dout = x.shape[-1], w1.shape[0], w2.shape[0]
+        xc = _c(x).reshape(-1, d)
+        T = xc.shape[0]
+        dev = x.device
+        if training and T < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+        if H.lib().gt_batchnorm_ws_bytes(T, f) == 0:      # refused before anything is launched
+            raise H.GtNotSupported(f"gt_batchnorm_fwd: no kernel for a hidden width of {f} (a multiple of 4 is needed)")
+        w1c, w2c, gc = _c(w1), _c(w2), _c(gamma)
+        salt = _next_salt()
+        hid = torch.empty(T, f, dtype=torch.float32, device=dev)
+        pre = torch.empty(T, f, dtype=torch.float32, device=dev) if act == H.ACT_SILU else None
+        out = torch.empty(T, dout, dtype=torch.float32, device=dev)
+        rc = None if res is None else _c(res).reshape(T, dout)
+        d_h = H.dropout_desc(p_h, salt, dev) if p_h > 0 else None
+        d_o = H.dropout_desc(p_out, salt + 1, dev) if p_out > 0 else None
+        H.gemm(xc, w1c, hid, T, f, d, lda=d, ldb=d, ldc=f, bias=b1, act=act, pre=pre, ldpre=f, drop=d_h, weight_b=True)
+        z, stats, _ = H.batchnorm_fwd(hid, gc, _c(beta), eps, running_mean, running_var, momentum, training)
+        H.gemm(z, w2c, out, T, dout, f, lda=f, ldb=f, ldc=dout, bias=b2, drop=d_o, res=rc, ldr=dout, weight_b=True)
+        ctx.save_for_backward(xc, w1c, w2c, hid, pre, z, gc, stats)
+        ctx.cfg = (act, p_h, p_out, salt, d, f, dout, b1 is not None, b2 is not None, res is not None, x.shape,
+                   bool(training))
+        ctx.in_mask = _wanted_mask(xc)            # the producer of x wants d(x) under its own output mask too
+        _hint_output_mask(out, p_out, salt + 1)
+        return out.reshape(*x.shape[:-1], dout)
+
+    @staticmethod
+    def backward(ctx, gy):
+        xc, w1c, w2c, hid, pre, z, gc, stats = ctx.saved_tensors
+        act, p_h, p_out, salt, d, f, dout, hb1, hb2, has_res, xshape, training = ctx.cfg
+        dev = gy.device
+        T = xc.shape[0]
+        g = _c(gy).reshape(T, dout)
+        gm = g
+        if p_out > 0:           # the masked copy the consumer of our output wrote next to d(out), else the elementwise pass
+            gm = _take_twin(g, p_out, salt + 1)
+            if gm is None:
+                gm = H.dropout_apply(g, H.dropout_desc(p_out, salt + 1, dev))
+        # weight gradients on the side stream, bias gradients as row sums of their A operand (as in FeedForwardFn)
+        dw2 = torch.empty(dout, f, dtype=torch.float32, device=dev)
+        db2 = torch.empty(dout, dtype=torch.float32, device=dev) if hb2 else None
+        with H.side_branch(dev, T):
+            H.gemm(gm, z, dw2, dout, f, T, layout_a=1, layout_b=1, lda=dout, ldb=f, ldc=f, split_k=0, a_colsum=db2)
+        # dz = gm W2, then the norm's backward with the activation / dropout gate on its store: gh is written once
+        dz = torch.empty(T, f, dtype=torch.float32, device=dev)
+        H.gemm(gm, w2c, dz, T, f, dout, layout_b=1, lda=dout, ldb=f, ldc=f, weight_b=True)
+        if act == H.ACT_RELU:
+            gate = (H.AUX_GT0, None, 1.0 / (1.0 - p_h), None)
+        else:
+            gate = (H.AUX_DSILU, pre, 1.0, H.dropout_desc(p_h, salt, dev) if p_h > 0 else None)
+        gh, dgamma, dbeta = H.batchnorm_bwd(hid, dz, gc, stats, training, gate=gate, out=dz)
+        dw1 = torch.empty(f, d, dtype=torch.float32, device=dev)
+        db1 = torch.empty(f, dtype=torch.float32, device=dev) if hb1 else None
+        with H.side_branch(dev, T):
+            H.gemm(gh, xc, dw1, f, d, T, layout_a=1, layout_b=1, lda=f, ldb=d, ldc=d, split_k=0, a_colsum=db1)
+        dx = torch.empty(T, d, dtype=torch.float32, device=dev)
+        same = has_res and dout == d
+        dxm, want = None, ctx.in_mask
+        if want is not None:
+            dxm = torch.empty_like(dx)
+        H.gemm(gh, w1c, dx, T, d, f, layout_b=1, lda=f, ldb=d, ldc=d, res=g if same else None, ldr=d, weight_b=True,
+               c_masked=dxm, ldc_masked=d, c_mask=H.dropout_desc(want[0], want[1], dev) if want else None)
+        if dxm is not None:
+            _offer_twin(dx, dxm, *want)
+        H.join_side(dev)
+        dx = dx.reshape(xshape)
+        dres = None if (not has_res or same) else gy      # res is x: its gradient is folded into dx
+        return (dx, dw1, db1, dw2, db2, dgamma, dbeta, None, None, dres) + (None,) * 6
+
+
+def feed_forward_bn(x, w1, b1, w2, b2, gamma, beta, running_mean, running_var, res=None, act="relu", p_h=0.0, p_out=0.0,
+                    eps=1e-5, momentum=0.1, training=True):
+    """FeedForward with BatchNorm1d(gamma, beta, running_mean, running_var) between the hidden dropout and lr2.  res must
+    be x itself (or None): the fused backward folds d(res) into d(x).  training=True updates the running buffers in place
+    (num_batches_tracked is the module's business); act: 'relu' or 'silu' -- 'gelu' raises NotImplementedError, the GEMM
+    epilogues and the norm's gate carry relu / silu only."""
+    _check_res_is_x(res, x, "feed_forward_bn")
+    return FeedForwardBNFn.apply(x, w1, b1, w2, b2, gamma, beta, running_mean, running_var, res, H.ACT_CODE[act],
+                                 float(p_h), float(p_out), float(eps), float(momentum), bool(training))

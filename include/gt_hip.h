@@ -437,6 +437,42 @@ int gt_token_norm_bwd(const float* X, const float* dY, const float* gamma, const
                       int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * BatchNorm1d of the FeedForward hidden activation: batch_norm=True of FeedForward (layers.py:979-987,
+ * nn.BatchNorm1d(dim_feedforward) on the transposed hidden tensor; ABI v21, additive).  X is the dense [T][f] hidden
+ * matrix, T = B n token rows; one mean and one BIASED variance per column c over all T rows:
+ *     z[t][c] = (x[t][c] - mean[c]) * rstd[c] * gamma[c] + beta[c],   rstd = 1 / sqrt(var + eps)
+ *     training != 0: batch statistics; running_mean <- (1 - m) running_mean + m mean and
+ *                    running_var <- (1 - m) running_var + m var T / (T - 1), in place, when the pointers are given
+ *     training == 0: mean / var are running_mean / running_var (required), nothing is updated
+ * gamma, beta, running_*, bvar, dgamma, dbeta: [f].  stats [f][2] = (mean, rstd) and bvar [f] (the biased variance, in
+ * eval mode a copy of running_var) are written by the forward; the backward reads stats.
+ *     forward : per-chunk Welford (mean, M2) partials relative to row 0 of the column, in ws; merged with the pairwise
+ *               update (never E[x^2] - mean^2) in two levels, each in a fixed order: the chunks of a group of 64 in chunk
+ *               order, then the groups in group order; then the applying pass.  The chunk length follows T (32 .. 128 rows,
+ *               longer beyond 4096 chunks), so no merge runs over more than 64 items
+ *     backward: xh = (x - mean) rstd from the RAW input X and stats (never z / gamma: a zero weight is legal);
+ *               dbeta = s1 = sum_t dZ, dgamma = s2 = sum_t dZ xh, summed in the same two levels (either may be NULL);
+ *               d = rstd gamma (dZ - s1/T - xh s2/T) in training mode, d = rstd gamma dZ in eval mode, and the store
+ *               carries the gate of what sits in front of the norm, gate_op of the gt_gemm_desc.aux_op vocabulary:
+ *                 GT_AUX_NONE   dX = d
+ *                 GT_AUX_GT0    dX = X > 0 ? d gate_scale : 0     (ReLU, dropout scale folded in; X is read anyway)
+ *                 GT_AUX_DSILU  dX = d silu'(gate_aux) mask       (gate_aux [T][f] = saved pre-activation; gate_drop, optional:
+ *                               mask index = the flat element index t f + c, the one gt_dropout_apply uses)
+ *               gate_drop with another gate: GT_EINVAL.  GT_AUX_MUL: GT_ENOTSUP.
+ * No atomics: bit-identical from run to run.  In place is allowed (Z == X; dX == dZ).  fp32 in every precision mode; the
+ * caller's stream, no allocation, no host read-back.  f % 4 != 0: GT_ENOTSUP (the ws query returns 0); X, dZ, gate_aux, Z,
+ * dX, stats, ws off a 16-byte boundary: GT_EALIGN; T < 2 in training mode: GT_EINVAL before anything is launched (one
+ * value per channel has no variance; torch refuses it too).  ws >= gt_batchnorm_ws_bytes, which serves both directions.
+ * ------------------------------------------------------------------------------------------- */
+int64_t gt_batchnorm_ws_bytes(int64_t T, int32_t f);
+int gt_batchnorm_fwd(const float* X, const float* gamma, const float* beta, float eps, float* running_mean,
+                     float* running_var, float momentum, int32_t training, float* Z, float* stats, float* bvar, int64_t T,
+                     int32_t f, void* ws, int64_t ws_bytes, void* stream);
+int gt_batchnorm_bwd(const float* X, const float* dZ, const float* gamma, const float* stats, float* dX, float* dgamma,
+                     float* dbeta, int64_t T, int32_t f, int32_t training, int32_t gate_op, const float* gate_aux,
+                     float gate_scale, const gt_dropout* gate_drop, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused Fourier-type attention (layers.py:672-705):  out = ((Q' K'^T) * scale .* mask) V'  on the head-tile
  * layout [B*n][h][DP], without writing the n x n score matrix: score tiles are scaled, masked (stateless
  * dropout with mask index ((b*h+head)*n + query)*n + key -- the index the materialising gt_gemm path uses --

@@ -1,7 +1,8 @@
 // Per-head LayerNorm of the Q / K / V projections with the position concat (gfx950): [T][3 h dk] -> head tiles
 // [3][T][h][DP] = [pos(p) | values(dk) | pad], forward and backward, in two generations: the LDS-staged kernels take any
 // shape, the bandwidth-shaped v2 kernels take dk % 4 == 0 with 16-byte aligned operands (head_geom decides).  The backward
-// leaves d(gamma), d(beta) partials per block; gt_slab_reduce sums them in a fixed order.
+// leaves d(gamma), d(beta) partials per block; gt_slab_reduce sums them in a fixed order.  gt_headtile_* do the same for ONE
+// stream with a row count and a leading dimension of its own (cross-attention: Q rows and K, V rows differ).
 #include "gt_common.h"
 
 namespace gt {
@@ -310,6 +311,175 @@ static bool head_geom(int T, int h, int dk, int p, int norm_mask, int max_blocks
     return true;
 }
 
+// ---- single-stream head tiles (cross-attention) ------------------------------------------------------
+// One stream of the above on its own row count: X [T][ldx] (a column block of a wider projection buffer) -> out [T][h][DP]
+// = [pos | values | zero pad], stats [T][h][2]; gamma == NULL: no norm.  The lane layout of the v2 kernels with PT = h*G
+// lanes per token: a lane owns the floats 4q .. 4q+3 of its head segment for the whole kernel.  VEC (dk % 4 == 0, 16-byte
+// aligned operands) moves them as float4; otherwise the same kernels move scalars and a segment's last lane holds
+// nv < 4 of them, so any dk up to 256 runs.
+struct StreamGeom {
+    int T, h, dk, p, DP, G, PT, R, tpb;
+    int64_t ldx, lddx;
+};
+
+template <bool VEC>
+__device__ __forceinline__ f32x4 lane_load(const float* __restrict__ src, int nv) {
+    if constexpr (VEC) return *reinterpret_cast<const f32x4*>(src);
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j < nv) v[j] = src[j];
+    return v;
+}
+template <bool VEC>
+__device__ __forceinline__ void lane_store(float* __restrict__ dst, int nv, f32x4 v) {
+    if constexpr (VEC) *reinterpret_cast<f32x4*>(dst) = v;
+    else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < nv) dst[j] = v[j];
+    }
+}
+__device__ __forceinline__ f32x4 keep_first(f32x4 v, int nv) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j >= nv) v[j] = 0.f;
+    return v;
+}
+__device__ __forceinline__ float sum4(f32x4 v) { return v[0] + v[1] + v[2] + v[3]; }
+
+// The per-row LayerNorm of one head segment spread over G lanes (x: this lane's floats, zeros past nv), stated once for the
+// two kernels below.  Forward: the centred values, with *mu and *rstd.
+__device__ __forceinline__ f32x4 seg_center(f32x4 x, int nv, int G, float inv, float eps, float* mu, float* rstd) {
+    *mu = group_sum(sum4(x), G) * inv;
+    const f32x4 c = keep_first(x - *mu, nv);
+    const float var = group_sum(sum4(c * c), G) * inv;
+    *rstd = 1.f / sqrtf(var + eps);
+    return c;
+}
+// Backward from the saved (mu, rstd): dx = rstd * (gy g - mean(gy g) - xh mean(gy g xh)); *xh_out for d(gamma).
+__device__ __forceinline__ f32x4 seg_norm_bwd(f32x4 x, f32x4 gy, f32x4 gm, int nv, int G, float inv, float mu, float rstd,
+                                              f32x4* xh_out) {
+    const f32x4 xh = keep_first((x - mu) * rstd, nv);
+    const f32x4 gg = gy * gm;
+    const float m1 = group_sum(sum4(gg), G) * inv;
+    const float m2 = group_sum(sum4(gg * xh), G) * inv;
+    *xh_out = xh;
+    return rstd * (gg - m1 - xh * m2);
+}
+
+template <bool VEC>
+__global__ void headtile_fwd_kernel(const float* __restrict__ X, const float* __restrict__ pos,
+                                    const float* __restrict__ gamma, const float* __restrict__ beta, StreamGeom g,
+                                    float eps, float* __restrict__ out, float* __restrict__ stats) {
+    const int r = threadIdx.x / g.PT, l = threadIdx.x % g.PT;
+    if (r >= g.R) return;
+    const int head = l / g.G, q = l % g.G;
+    const int nv = max(0, min(4, g.dk - 4 * q));
+    const bool normed = gamma != nullptr;
+    f32x4 gm = {1.f, 1.f, 1.f, 1.f}, bt = {0.f, 0.f, 0.f, 0.f};
+    if (normed && nv > 0) {
+        gm = lane_load<VEC>(gamma + head * g.dk + 4 * q, nv);
+        bt = lane_load<VEC>(beta + head * g.dk + 4 * q, nv);
+    }
+    const float inv = 1.f / (float)g.dk;
+    const int t_end = min(g.T, (int)(blockIdx.x + 1) * g.tpb);
+    for (int t = blockIdx.x * g.tpb + r; t < t_end; t += g.R) {
+        f32x4 y = {0.f, 0.f, 0.f, 0.f};
+        if (nv > 0) y = lane_load<VEC>(X + (int64_t)t * g.ldx + head * g.dk + 4 * q, nv);
+        if (normed) {
+            float mu, rstd;
+            y = seg_center(y, nv, g.G, inv, eps, &mu, &rstd) * rstd * gm + bt;
+            if (q == 0) {
+                float* st = stats + ((int64_t)t * g.h + head) * 2;
+                st[0] = mu;
+                st[1] = rstd;
+            }
+        }
+        float* row = out + ((int64_t)t * g.h + head) * g.DP;
+        if (nv > 0) {
+            if constexpr (VEC) tile_store4(row + g.p + 4 * q, g.p, y);
+            else lane_store<false>(row + g.p + 4 * q, nv, y);
+        }
+        if (q == 0) {
+            for (int j = 0; j < g.p; ++j) row[j] = pos[(int64_t)t * g.p + j];
+            for (int j = g.p + g.dk; j < g.DP; ++j) row[j] = 0.f;
+        }
+    }
+}
+
+template <bool VEC>
+__global__ void headtile_bwd_kernel(const float* __restrict__ d_out, const float* __restrict__ X,
+                                    const float* __restrict__ gamma, const float* __restrict__ stats, StreamGeom g,
+                                    float* __restrict__ dX, float* __restrict__ partial /* [nblk][dg: h*dk | db: h*dk] */) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];      // [R][PT][8]
+    const int r = threadIdx.x / g.PT, l = threadIdx.x % g.PT;
+    const int hd = g.h * g.dk;
+    const bool normed = gamma != nullptr;
+    if (r < g.R) {
+        const int head = l / g.G, q = l % g.G;
+        const int nv = max(0, min(4, g.dk - 4 * q));
+        f32x4 gm = {1.f, 1.f, 1.f, 1.f};
+        if (normed && nv > 0) gm = lane_load<VEC>(gamma + head * g.dk + 4 * q, nv);
+        f32x4 dg = {0.f, 0.f, 0.f, 0.f}, db = {0.f, 0.f, 0.f, 0.f};
+        const float inv = 1.f / (float)g.dk;
+        const int t_end = min(g.T, (int)(blockIdx.x + 1) * g.tpb);
+        for (int t = blockIdx.x * g.tpb + r; t < t_end; t += g.R) {
+            f32x4 gy = {0.f, 0.f, 0.f, 0.f}, x = {0.f, 0.f, 0.f, 0.f};
+            if (nv > 0) {
+                const float* row = d_out + ((int64_t)t * g.h + head) * g.DP + g.p + 4 * q;
+                if constexpr (VEC) gy = tile_load4(row, g.p);
+                else gy = lane_load<false>(row, nv);
+                if (normed) x = lane_load<VEC>(X + (int64_t)t * g.ldx + head * g.dk + 4 * q, nv);
+            }
+            f32x4 dx = gy;
+            if (normed) {
+                const float* st = stats + ((int64_t)t * g.h + head) * 2;
+                f32x4 xh;
+                dx = seg_norm_bwd(x, gy, gm, nv, g.G, inv, st[0], st[1], &xh);
+                dg += gy * xh;
+                db += gy;
+            }
+            if (nv > 0) lane_store<VEC>(dX + (int64_t)t * g.lddx + head * g.dk + 4 * q, nv, dx);
+        }
+        if (normed) {
+            float* me = lds + ((size_t)r * g.PT + l) * 8;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { me[j] = dg[j]; me[4 + j] = db[j]; }
+        }
+    }
+    if (!normed) return;
+    __syncthreads();
+    // fixed-order combine over the R token rows, one thread per (lane slot, component)
+    float* pg = partial + (int64_t)blockIdx.x * 2 * hd;
+    for (int e = threadIdx.x; e < g.PT * 8; e += blockDim.x) {
+        const int ll = e >> 3, comp = e & 7;
+        const int head = ll / g.G, c = 4 * (ll % g.G) + (comp & 3);
+        if (c >= g.dk) continue;
+        float s = 0.f;
+        for (int rr = 0; rr < g.R; ++rr) s += lds[((size_t)rr * g.PT + ll) * 8 + comp];
+        pg[(comp < 4 ? 0 : hd) + head * g.dk + c] = s;
+    }
+}
+
+static bool stream_geom(int T, int h, int dk, int p, int64_t ldx, int64_t lddx, int max_blocks, StreamGeom* g, int* threads,
+                        int* blocks) {
+    int G = 1;
+    while (G < (dk + 3) / 4) G <<= 1;
+    if (G > 64) return false;
+    const int PT = h * G;                  // a multiple of G, G | 64: no segment's lanes straddle a wave
+    if (PT > 1024) return false;
+    const int thr = std::max(256, ((PT + 63) / 64) * 64);
+    const int R = thr / PT;
+    int nblk = std::max(1, std::min(max_blocks, ceil_div(T, R * 8)));
+    const int tpb = ceil_div(ceil_div(T, nblk), R) * R;
+    nblk = ceil_div(T, tpb);
+    *g = StreamGeom{T, h, dk, p, (dk + p + 3) & ~3, G, PT, R, tpb, ldx, lddx};
+    *threads = thr;
+    *blocks = nblk;
+    return true;
+}
+
 static inline int hn_tok_bwd(int h, int dk) { return hn_tok(2 * 3 * h * (dk + 1) + 9 * h); }
 constexpr int HN_MAXB = 1024;      // bound on blocks (= dgamma/dbeta partials) of the backward
 static inline int hn_blocks_bwd(int T, int h, int dk) { return std::min(ceil_div(T, hn_tok_bwd(h, dk)), HN_MAXB); }
@@ -377,6 +547,49 @@ extern "C" int gt_headnorm_bwd(const float* d_out, const float* qkv, const float
         // partial: [nblk][ (dg: 2*hd) | (db: 2*hd) ]
         if (int rc = gt_slab_reduce(partial, 4 * hd, nblk, 2 * hd, 1.f, dgamma, stream)) return rc;
         return gt_slab_reduce(partial + 2 * hd, 4 * hd, nblk, 2 * hd, 1.f, dbeta, stream);
+    }
+    return 0;
+}
+
+extern "C" int gt_headtile_fwd(const float* X, int64_t ldx, const float* pos, const float* gamma, const float* beta,
+                               int32_t T, int32_t h, int32_t dk, int32_t p, float eps, float* out, float* stats,
+                               void* stream) {
+    if (!X || !out || T <= 0 || h <= 0 || dk <= 0 || p < 0 || ldx < (int64_t)h * dk) return GT_EINVAL;
+    if (p > 0 && !pos) return GT_EINVAL;
+    if (gamma && (!beta || !stats)) return GT_EINVAL;
+    StreamGeom g; int thr, nblk;
+    if (!stream_geom(T, h, dk, p, ldx, 0, 1 << 20, &g, &thr, &nblk)) return GT_ENOTSUP;
+    const bool vec = !(dk & 3) && !(ldx & 3) && !misaligned16(X, out, gamma, beta) && !misaligned<8>(stats);
+    hipLaunchKernelGGL(vec ? headtile_fwd_kernel<true> : headtile_fwd_kernel<false>, dim3(nblk), dim3(thr), 0,
+                       (hipStream_t)stream, X, pos, gamma, beta, g, eps, out, stats);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int64_t gt_headtile_bwd_ws_bytes(int32_t T, int32_t h, int32_t dk) {
+    (void)T;
+    return (int64_t)HN_MAXB * 2 * h * dk * (int64_t)sizeof(float);
+}
+
+extern "C" int gt_headtile_bwd(const float* d_out, const float* X, int64_t ldx, const float* gamma, const float* stats,
+                               int32_t T, int32_t h, int32_t dk, int32_t p, float* dX, int64_t lddx, float* dgamma,
+                               float* dbeta, void* ws, int64_t ws_bytes, void* stream) {
+    if (!d_out || !dX || T <= 0 || h <= 0 || dk <= 0 || p < 0 || lddx < (int64_t)h * dk) return GT_EINVAL;
+    if (gamma && (!X || ldx < (int64_t)h * dk || !stats || !dgamma || !dbeta)) return GT_EINVAL;
+    if (gamma && (!ws || ws_bytes < gt_headtile_bwd_ws_bytes(T, h, dk))) return GT_EWS;
+    StreamGeom g; int thr, nblk;
+    if (!stream_geom(T, h, dk, p, ldx, lddx, HN_MAXB, &g, &thr, &nblk)) return GT_ENOTSUP;
+    const bool vec = !(dk & 3) && !(lddx & 3) && !(gamma && (ldx & 3)) && 
+                     !misaligned16(d_out, dX, gamma ? X : (const float*)nullptr, gamma);
+    const size_t lds = gamma ? (size_t)g.R * g.PT * 8 * sizeof(float) : 0;
+    float* partial = reinterpret_cast<float*>(ws);
+    hipLaunchKernelGGL(vec ? headtile_bwd_kernel<true> : headtile_bwd_kernel<false>, dim3(nblk), dim3(thr), lds,
+                       (hipStream_t)stream, d_out, X, gamma, stats, g, dX, partial);
+    GT_LAUNCH_CHECK();
+    if (gamma) {
+        const int hd = h * dk;
+        if (int rc = gt_slab_reduce(partial, 2 * hd, nblk, hd, 1.f, dgamma, stream)) return rc;
+        return gt_slab_reduce(partial + hd, 2 * hd, nblk, hd, 1.f, dbeta, stream);
     }
     return 0;
 }

@@ -98,6 +98,10 @@ _PROTOS = {
     "gt_headnorm_bwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p] * 4 + [C.c_int64,
                                                                                         C.c_void_p]),
     "gt_headnorm_bwd_ws_bytes": (C.c_int64, [C.c_int32] * 3),
+    "gt_headtile_fwd": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_float] + [C.c_void_p] * 3),
+    "gt_headtile_bwd_ws_bytes": (C.c_int64, [C.c_int32] * 3),
+    "gt_headtile_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int32] * 4
+                        + [C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
     "gt_galerkin_ktv_slabs": (C.c_int32, [C.c_int32, C.c_int32]),
     "gt_galerkin_ktv": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_int32, C.c_void_p]),
     "gt_galerkin_ktv_affine": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p, C.c_int32, C.c_void_p]),
@@ -930,6 +934,32 @@ def headnorm_bwd(d_out: torch.Tensor, qkv: torch.Tensor, gamma: Optional[torch.T
     ws = workspace(dev, lib().gt_headnorm_bwd_ws_bytes(T, h, dk))
     _launch("gt_headnorm_bwd", d_out, qkv, gamma, stats, T, h, dk, p, norm_mask, d_qkv, dgamma, dbeta, ws=ws)
     return d_qkv, dgamma, dbeta
+
+
+def headtile_fwd(X: torch.Tensor, ldx: int, pos: Optional[torch.Tensor], gamma: Optional[torch.Tensor],
+                 beta: Optional[torch.Tensor], T: int, h: int, dk: int, p: int, eps: float):
+    """One stream X [T, ldx] (a column block of a projection buffer) -> head tiles out [T, h, DP], stats [T, h, 2] (None
+    without gamma [h, dk]: copy, coordinates and zero pad only)."""
+    need_f32_cuda(X, pos, gamma, beta)
+    out = torch.empty(T, h, round4(dk + p), dtype=torch.float32, device=X.device)
+    stats = torch.empty(T, h, 2, dtype=torch.float32, device=X.device) if gamma is not None else None
+    _launch("gt_headtile_fwd", X, ldx, pos, gamma, beta, T, h, dk, p, eps, out, stats,
+            nbytes=4.0 * T * h * (dk + round4(dk + p)), shape=(T, h, dk, p))
+    return out, stats
+
+
+def headtile_bwd(d_out: torch.Tensor, X: Optional[torch.Tensor], ldx: int, gamma: Optional[torch.Tensor],
+                 stats: Optional[torch.Tensor], T: int, h: int, dk: int, p: int, dX: torch.Tensor, lddx: int,
+                 dgamma: Optional[torch.Tensor] = None, dbeta: Optional[torch.Tensor] = None):
+    """Backward of headtile_fwd: the value columns of d_out [T, h, DP] (through the LayerNorm backward when gamma is given)
+    into dX [T, lddx], a column block of a gradient buffer; dgamma / dbeta [h, dk] are contiguous views to fill."""
+    need_f32_cuda(d_out, X, gamma, stats, dX, dgamma, dbeta)
+    if gamma is not None and not (dgamma.is_contiguous() and dbeta.is_contiguous()):
+        raise ValueError("headtile_bwd: dgamma / dbeta must be contiguous")
+    ws = workspace(dX.device, max(16, lib().gt_headtile_bwd_ws_bytes(T, h, dk)))
+    _launch("gt_headtile_bwd", d_out, X, ldx, gamma, stats, T, h, dk, p, dX, lddx, dgamma, dbeta, ws=ws,
+            nbytes=4.0 * T * h * (2 * dk + round4(dk + p)), shape=(T, h, dk, p))
+    return dX
 
 
 def galerkin_finalize_fwd(slabs: torch.Tensor, n_slabs: int, slab_stride: int, B: int, h: int, DP: int,

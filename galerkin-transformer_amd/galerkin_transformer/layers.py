@@ -320,8 +320,8 @@ class SimpleAttention(nn.Module):
 
     Same parameters / state_dict keys as the reference (layers.py:793-828): ``linears.{0,1,2}``,
     ``norm_K.{i}``, ``norm_V.{i}`` (galerkin) or ``norm_Q.{i}`` (fourier, softmax), ``fc``.  The HIP path covers
-    self-attention (query is key is value) of the 'galerkin', 'linear' / 'global', 'fourier' ('integral', 'local') and
-    'softmax' types with norm_type='layer', and the Galerkin family with norm_type='instance': ``norm_K`` / ``norm_V`` are then
+    self-attention (query is key is value) and cross-attention (below) of the 'galerkin', 'linear' / 'global', 'fourier'
+    ('integral', 'local') and 'softmax' types with norm_type='layer', and the Galerkin family with norm_type='instance': ``norm_K`` / ``norm_V`` are then
     ``nn.InstanceNorm1d(d_k, affine=True)`` per head (same keys and shapes, no buffers) and K, V are normalised over the
     tokens, one mean and variance per (sample, head, channel), before the coordinates are concatenated (layers.py:842-854).
     'softmax' (scaled dot-product attention, the dropout mask on the softmax output; fp32 arithmetic in every precision
@@ -330,6 +330,12 @@ class SimpleAttention(nn.Module):
     'fourier' with ``need_weights=False`` is fused (no n x n matrix in HBM) at the same five head-tile widths in every
     precision mode: the two-term fp16 kernel in the default arithmetic, the fp32-MFMA kernel (gt_fourier_attn, and
     gt_fourier_attn_wide at 68 / 100) under ``set_precision('f32')`` and the bf16 modes; other widths materialise.
+    Cross-attention: ``forward(query, key, value, pos)`` with the three not one tensor (fused_forward_cross,
+    ops.cross_attention) projects query [B, n_q, d] through linears[0] and key, value [B, n_kv, d] through linears[1], [2].
+    The Galerkin family takes any n_q, n_kv without coordinates (with ``pos`` the same coordinates go to all three, so the
+    counts are equal) and divides K'^T V' -- a sum over the n_kv memory tokens -- by n_q, as the reference does
+    (layers.py:719, 728); fourier / softmax need n_q == n_kv (NotImplementedError otherwise).  Unequal key / value token
+    counts, unequal batch sizes and ``pos`` with n_q != n_kv are AssertionErrors.
     Other variants of the reference are baselines outside the hot path."""
 
     def __init__(self, n_head, d_model, pos_dim: int = 1, attention_type="fourier", dropout=0.1,
@@ -418,9 +424,9 @@ class SimpleAttention(nn.Module):
             beta = beta.view(2, self.n_head, self.d_k)
         return wqkv, bqkv, gamma, beta, mask
 
-    def fused_forward(self, x, pos=None, residual=None, sign=1.0, p_out=0.0, need_weights=True):
-        """res + sign*dropout(attention(x)); the encoder layer's entry point.  ``need_weights=False`` lets the
-        Fourier and softmax types run fused (no n x n matrix in HBM; the returned weight is None)."""
+    def _operator_args(self, pos, device):
+        """What the self- and the cross-attention operator share: the checks of the attention type, then
+        (pos or None, wfc, bfc, kind)."""
         if self.attention_type in _SOFTMAX_ATTENTION and (pos is None or self.pos_dim == 0):
             raise NotImplementedError("attention_type='softmax' without coordinates is outside the HIP hot path: the softmax "
                                       "kernels take head tiles of width 16*k + 4 (d_k in (16, 32, 48, 64, 96) plus pos_dim >= 1)")
@@ -436,11 +442,10 @@ class SimpleAttention(nn.Module):
             # the same operator with zero coordinate columns and the identity in fc's place
             pos = None
             d = self.n_head * self.d_k
-            key = (x.device, d)
+            key = (device, d)
             if getattr(self, "_eye", (None, None))[0] != key:
-                self._eye = (key, torch.eye(d, dtype=torch.float32, device=x.device))
+                self._eye = (key, torch.eye(d, dtype=torch.float32, device=device))
             wfc, bfc = self._eye[1], None
-        wqkv, bqkv, gamma, beta, mask = self._packed()
         if self.attention_type == "galerkin":
             kind = "galerkin"
         elif self.attention_type in ("linear", "global"):     # the reference treats the two names alike (layers.py:719)
@@ -449,10 +454,31 @@ class SimpleAttention(nn.Module):
             kind = "softmax"
         else:
             kind = "fourier"
+        return pos, wfc, bfc, kind
+
+    def fused_forward(self, x, pos=None, residual=None, sign=1.0, p_out=0.0, need_weights=True):
+        """res + sign*dropout(attention(x)); the encoder layer's entry point.  ``need_weights=False`` lets the
+        Fourier and softmax types run fused (no n x n matrix in HBM; the returned weight is None)."""
+        pos, wfc, bfc, kind = self._operator_args(pos, x.device)
+        wqkv, bqkv, gamma, beta, mask = self._packed()
         out, w = ops.simple_attention(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc,
                                       kind=kind, n_head=self.n_head, norm_mask=mask, eps=self.eps,
                                       res=residual, sign=sign, p_out=p_out, need_weights=need_weights,
                                       token_norm=self.add_norm and self.norm_type == "instance")
+        self.attn_weight = w
+        return out, w
+
+    def fused_forward_cross(self, query, key, value, pos=None, residual=None, sign=1.0, p_out=0.0, need_weights=True):
+        """The same for query [B, n_q, d], key and value [B, n_kv, d] that are not one tensor (ops.cross_attention):
+        res + sign*dropout(attention(query, key, value)) with ``residual`` = ``query`` or None.  Shape contracts are
+        AssertionErrors, raised before anything is launched."""
+        ops.check_cross_shapes(query, key, value, pos if self.pos_dim > 0 else None)
+        pos, wfc, bfc, kind = self._operator_args(pos, query.device)
+        wqkv, bqkv, gamma, beta, mask = self._packed()
+        out, w = ops.cross_attention(query, key, value, pos, wqkv, bqkv, gamma, beta, wfc, bfc,
+                                     kind=kind, n_head=self.n_head, norm_mask=mask, eps=self.eps,
+                                     res=residual, sign=sign, p_out=p_out, need_weights=need_weights,
+                                     token_norm=self.add_norm and self.norm_type == "instance")
         self.attn_weight = w
         return out, w
 
@@ -464,7 +490,7 @@ class SimpleAttention(nn.Module):
         if weight is not None:
             raise NotImplementedError("weighted attention is outside the HIP hot path")
         if not (query is key and key is value):
-            raise NotImplementedError("the HIP path implements self-attention (query is key is value)")
+            return self.fused_forward_cross(query, key, value, pos)
         return self.fused_forward(query, pos)
 
 

@@ -1,5 +1,5 @@
 """The attention node: dropout mode and mask queue, the shared projection stage, the galerkin / linear, fourier and
-softmax cores, SimpleAttentionFn.
+softmax cores, SimpleAttentionFn; CrossAttentionFn (query, key, value not one tensor) on the same cores.
 """
 from __future__ import annotations
 
@@ -170,26 +170,29 @@ def _merged_fc_bwd(s, g, dims, sign, hbf):
     return datt, dwfc, dbfc
 
 
-def _galerkin_fwd(kind, Qp, Kp, Vp, out, rc, wf, bfc, affine, mask, d_attn, d_out, dims, sign):
+def _galerkin_fwd(kind, Qp, Kp, Vp, out, rc, wf, bfc, affine, mask, d_attn, d_out, dims, sign, n_kv=None):
     """galerkin / linear core: M = mask .* (K'^T V')/n, out = res + sign * dropout(fc(Q' M)).  ``affine`` = (gamma, beta) for
-    "plain" tiles, else (None, None).  Returns (attn_weight, tensors to save)."""
+    "plain" tiles, else (None, None).  ``n_kv`` (cross-attention): K', V' hold n_kv tokens per sample, Q' and out n; the sum
+    of K'^T V' runs over the n_kv memory tokens and the divisor stays n, the QUERY count (layers.py:719, 728).  Returns
+    (attn_weight, tensors to save)."""
     B, n, d, h, dk, p, Dr, DP = dims
     hD, dev = h * DP, out.device
+    m = n if n_kv is None else n_kv     # tokens of K', V'
     # gt_galerkin_ktv reads the coordinate columns once, from K', for both operands: right for [pos, K], [pos, V]
     streaming = True
     if kind == "linear":
         # Q~ = softmax over the head's columns, K~ = softmax over the tokens, both in place: the backward needs the
         # softmax outputs only, and the LayerNorm backward of K reads the raw projection, not the tiles
         H.feature_softmax_fwd(Qp, B * n * h, dk, p, out=Qp)
-        H.token_softmax_fwd(Kp, B, n, h, dk, p, out=Kp)
+        H.token_softmax_fwd(Kp, B, m, h, dk, p, out=Kp)
         # ... not for K~, whose coordinate columns went through the token softmax: with coordinates the full tiles are
         # contracted through gt_gemm below
         streaming = p == 0
-    slabs = H.galerkin_ktv(Kp, Vp, B, n, h, dk, p, gamma=affine[0], beta=affine[1]) if streaming else None
+    slabs = H.galerkin_ktv(Kp, Vp, B, m, h, dk, p, gamma=affine[0], beta=affine[1]) if streaming else None
     if slabs is None:                                       # head sizes the streaming MFMA kernel does not cover
         slabs = torch.empty(1, B, h, DP, DP, dtype=torch.float32, device=dev)
-        H.gemm(Kp, Vp, slabs, DP, DP, n, layout_a=1, layout_b=1, lda=hD, ldb=hD, ldc=DP, batch=(B, h),
-               a_bs=(n * hD, DP), b_bs=(n * hD, DP), c_bs=(h * DP * DP, DP * DP), split_k=0)
+        H.gemm(Kp, Vp, slabs, DP, DP, m, layout_a=1, layout_b=1, lda=hD, ldb=hD, ldc=DP, batch=(B, h),
+               a_bs=(m * hD, DP), b_bs=(m * hD, DP), c_bs=(h * DP * DP, DP * DP), split_k=0)
     Mt, P, Pv = H.galerkin_finalize_fwd(slabs, slabs.shape[0], B * h * DP * DP, B, h, DP, Dr, d, n, mask,
                                         d_attn, wf, value_rows_of=p)
     H.gemm(Qp, P, out, n, d, hD, layout_b=1, lda=hD, ldb=d, ldc=d, batch=(B, 1), a_bs=(n * hD, 0),
@@ -198,11 +201,13 @@ def _galerkin_fwd(kind, Qp, Kp, Vp, out, rc, wf, bfc, affine, mask, d_attn, d_ou
     return Mt[:, :, :Dr, :Dr], dict(wf=wf, Mt=Mt, P=P, Pv=Pv)
 
 
-def _galerkin_bwd(kind, s, g, d_attn, dims, sign, hbf, token_norm, plain, fused_ln):
+def _galerkin_bwd(kind, s, g, d_attn, dims, sign, hbf, token_norm, plain, fused_ln, n_kv=None):
     """Backward of _galerkin_fwd from the masked gradient g [T, d].  Returns (dO3, ln, dwfc, dbfc): the gradient tiles, or
-    with ``fused_ln`` ln = (d_qkv, dgamma, dbeta) from gt_galerkin_dkv_ln and dO3 = None."""
+    with ``fused_ln`` ln = (d_qkv, dgamma, dbeta) from gt_galerkin_dkv_ln and dO3 = None.  With ``n_kv`` (never together with
+    ``fused_ln``) dO3 is a triple of tiles: dQ' [B*n, h, DP], dK' and dV' [B*n_kv, h, DP]."""
     B, n, d, h, dk, p, Dr, DP = dims
     T, hD, dev = B * n, h * DP, g.device
+    m = n if n_kv is None else n_kv     # tokens of K', V'
     dbfc = torch.empty(d, dtype=torch.float32, device=dev) if hbf else None
     # (token_norm: the contractions ran on the normalised pair; out3[1:] are the raw tiles)
     Qp, (Kp, Vp) = s.out3[0], (s.kvn if token_norm else s.out3[1:])
@@ -222,7 +227,10 @@ def _galerkin_bwd(kind, s, g, d_attn, dims, sign, hbf, token_norm, plain, fused_
         H.gemm(g, s.Pv, dqkv, n, d, d, lda=d, ldb=d, ldc=3 * d, batch=(B, 1), a_bs=(n * d, 0),
                b_bs=(d * d, 0), c_bs=(n * 3 * d, 0), alpha=sign)
     else:
-        dO3 = torch.empty(3, T, h, DP, dtype=torch.float32, device=dev)
+        if n_kv is None:
+            dO3 = torch.empty(3, T, h, DP, dtype=torch.float32, device=dev)
+        else:
+            dO3 = tuple(torch.empty(B * r, h, DP, dtype=torch.float32, device=dev) for r in (n, m, m))
         H.gemm(g, s.P, dO3[0], n, hD, d, lda=d, ldb=d, ldc=hD, batch=(B, 1), a_bs=(n * d, 0),
                b_bs=(hD * d, 0), c_bs=(n * hD, 0), alpha=sign)
     H.join_side(dev)
@@ -235,17 +243,17 @@ def _galerkin_bwd(kind, s, g, d_attn, dims, sign, hbf, token_norm, plain, fused_
         ln = H.galerkin_dkv_ln(Kp, Vp, dM, None, s.qkv, s.gamma, s.stats, B, n, h, dk, p, d_qkv=dqkv,
                                beta=s.beta if plain else None)
     elif DP in H.FOURIER_DP:                           # one streaming pass (gt_galerkin_dkv)
-        H.galerkin_dkv(Kp, Vp, dM, dO3[1], dO3[2], B, n, h, DP)
+        H.galerkin_dkv(Kp, Vp, dM, dO3[1], dO3[2], B, m, h, DP)
     else:
-        H.gemm(Vp, dM, dO3[1], n, DP, DP, lda=hD, ldb=DP, ldc=hD, batch=(B, h), a_bs=(n * hD, DP),
-               b_bs=(h * DP * DP, DP * DP), c_bs=(n * hD, DP))
-        H.gemm(Kp, dM, dO3[2], n, DP, DP, layout_b=1, lda=hD, ldb=DP, ldc=hD, batch=(B, h),
-               a_bs=(n * hD, DP), b_bs=(h * DP * DP, DP * DP), c_bs=(n * hD, DP))
+        H.gemm(Vp, dM, dO3[1], m, DP, DP, lda=hD, ldb=DP, ldc=hD, batch=(B, h), a_bs=(m * hD, DP),
+               b_bs=(h * DP * DP, DP * DP), c_bs=(m * hD, DP))
+        H.gemm(Kp, dM, dO3[2], m, DP, DP, layout_b=1, lda=hD, ldb=DP, ldc=hD, batch=(B, h),
+               a_bs=(m * hD, DP), b_bs=(h * DP * DP, DP * DP), c_bs=(m * hD, DP))
     if kind == "linear":
         # (the softmax backwards sit between dK' and the LayerNorm backward, so the fused kernel never applies here)
         # Qp, Kp hold Q~, K~: dQ' = Q~ .* (dQ~ - sum_c Q~ dQ~), dK' = K~ .* (dK~ - sum_t K~ dK~), in place
         H.feature_softmax_bwd(Qp, dO3[0], T * h, dk, p, out=dO3[0])
-        H.token_softmax_bwd(Kp, dO3[1], B, n, h, dk, p, out=dO3[1])
+        H.token_softmax_bwd(Kp, dO3[1], B, m, h, dk, p, out=dO3[1])
     return dO3, ln, dwfc, dbfc
 
 
@@ -507,4 +515,202 @@ def simple_attention(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, *, kind: str, n_
     cfg = (kind, int(n_head), int(norm_mask), float(eps), float(sign), float(p_attn), float(p_out),
            bool(need_weights), bool(token_norm))
     out, w = SimpleAttentionFn.apply(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, cfg, mask)
+    return out, (w if w.numel() else None)
+
+
+# ----------------------------------------------------------------------------------- cross-attention
+# which of (query, key, value) are one tensor -> the projection groups (first stream, number of streams): a group is one
+# input, one product against its rows of the packed weight, one data-gradient and one weight-gradient product
+_CROSS_GROUPS = {"none": ((0, 1), (1, 1), (2, 1)), "kv": ((0, 1), (1, 2)), "qk": ((0, 2), (2, 1))}
+
+
+def _stream_norm(s, norm_mask, token_norm):
+    """Index into gamma / beta [2, h, dk] of stream s (0 = Q, 1 = K, 2 = V) when the head LayerNorm runs on it, else None."""
+    if token_norm or not (norm_mask >> s) & 1:
+        return None
+    return bin(norm_mask & ((1 << s) - 1)).count("1")
+
+
+def check_cross_shapes(query, key, value, pos):
+    """The shape contracts of cross-attention, AssertionErrors raised before anything is launched."""
+    assert query.dim() == 3 and key.dim() == 3 and value.dim() == 3 and query.size(-1) == key.size(-1) == value.size(-1), \
+        "cross_attention: query, key, value are [B, n, d]"
+    assert query.size(0) == key.size(0) == value.size(0), \
+        f"cross_attention: batch sizes differ ({query.size(0)}, {key.size(0)}, {value.size(0)})"
+    assert key.size(1) == value.size(1), f"cross_attention: key has {key.size(1)} tokens, value {value.size(1)}"
+    assert pos is None or (query.size(1) == key.size(1) == pos.size(1)), \
+        f"cross_attention: pos is concatenated to Q, K and V alike, so n_q = {query.size(1)}, n_kv = {key.size(1)} and " \
+        f"pos.size(1) = {pos.size(1)} must be equal"
+
+
+class CrossAttentionFn(Function):
+    """SimpleAttentionFn for query [B, n_q, d], key and value [B, n_kv, d] that are not one tensor (layers.py:829-899):
+    Q = linears[0](query), K = linears[1](key), V = linears[2](value), then the same head norms, cores and fc.
+
+    ``share`` names the inputs that are one tensor: "kv" (key is value; the ``value`` argument is None), "qk" (query is key;
+    ``key`` is None) or "none".  Projection: one plain gt_gemm per distinct input against its contiguous rows of the packed
+    weight (N = 2d for a shared pair), then gt_headtile_fwd per stream on its column block, then the token norm of K, V
+    (norm_type='instance').  Cores: _galerkin_fwd / _galerkin_bwd with n_kv (never the plain / fused_ln routes, which
+    assume one joint [T, 3 h dk] gradient buffer), _fourier_* / _softmax_* as they are (n_q == n_kv).  Backward:
+    gt_headtile_bwd per stream into its column block, then per input one data-gradient and one weight-gradient product (the
+    latter on the side branch, the bias gradient on its a_colsum); a shared input's two contributions are summed by its one
+    data-gradient product over K = 2d.  ``res`` must be ``query``.  No part in the dropout-mask hand-off of ops/_handoff.py."""
+
+    @staticmethod
+    def forward(ctx, query, key, value, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, cfg, mask):
+        (kind, h, norm_mask, eps, sign, p_attn, p_out, need_w, token_norm, share) = cfg
+        if kind not in ("galerkin", "linear", "fourier", "softmax"):
+            raise ValueError(f"cross_attention: kind={kind!r}")
+        if token_norm and (kind in ("fourier", "softmax") or norm_mask != 0b110 or gamma is None or beta is None):
+            raise ValueError("cross_attention: token_norm is the K, V norm of the galerkin / linear kinds")
+        H.need_f32_cuda(query, key, value, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, mask)
+        groups = _CROSS_GROUPS[share]
+        xs = {"none": (query, key, value), "kv": (query, key, key), "qk": (query, query, value)}[share]
+        B, n, d = query.shape
+        m = xs[1].shape[1]
+        dk = d // h
+        p = 0 if pos is None else pos.shape[-1]
+        Dr, DP = dk + p, H.round4(dk + p)
+        dev = query.device
+        assert kind in ("galerkin", "linear") or n == m, (kind, n, m)      # (cross_attention refuses it with its reason)
+        if (kind == "linear" or token_norm) and not H.linattn_supported(dk, p):
+            raise H.GtNotSupported(f"cross_attention: head size d_k={dk}, pos_dim={p} has no softmax / token-norm kernel")
+        if kind == "softmax" and DP not in H.SOFTMAX_DP + H.SOFTMAX_DP_WIDE:
+            raise H.GtNotSupported(f"softmax attention: head tile width round4(d_k + pos_dim) = {DP} has no kernel")
+        dims = (B, n, d, h, dk, p, Dr, DP)
+        rows = (B * n, B * m, B * m)
+        posc = None if pos is None else _c(pos).reshape(B * n, p)
+        wq, wf = _c(wqkv), _c(wfc)
+        salt = _next_salt(4)
+        xcs, projs, tiles, stats = [None] * 3, [None] * 3, [None] * 3, [None] * 3     # (xcs, projs: by the group's first stream)
+        for s0, ns in groups:
+            T = rows[s0]
+            xc = xcs[s0] = _c(xs[s0]).reshape(T, d)
+            proj = torch.empty(T, ns * d, dtype=torch.float32, device=dev)
+            H.gemm(xc, wq[s0 * d:(s0 + ns) * d], proj, T, ns * d, d, lda=d, ldb=d, ldc=ns * d,
+                   bias=None if bqkv is None else bqkv[s0 * d:(s0 + ns) * d])
+            for s in range(s0, s0 + ns):
+                ni = _stream_norm(s, norm_mask, token_norm)
+                tiles[s], stats[s] = H.headtile_fwd(proj[:, (s - s0) * d:], ns * d, posc, None if ni is None else gamma[ni],
+                                                    None if ni is None else beta[ni], T, h, dk, p, eps)
+                if ni is not None:      # the LayerNorm backward reads the raw projection
+                    projs[s0] = proj
+        kvn_k = kvn_v = st_k = st_v = None
+        if token_norm:
+            # tiles[1:] keep the raw K, V for the backward; the normalised pair is what the core reads and rewrites
+            kvn_k, st_k = H.token_norm_fwd(tiles[1], gamma[0], beta[0], eps, B, m, h, dk, p)
+            kvn_v, st_v = H.token_norm_fwd(tiles[2], gamma[1], beta[1], eps, B, m, h, dk, p)
+        Qp, Kp, Vp = (tiles[0], kvn_k, kvn_v) if token_norm else tiles
+        out = torch.empty(B * n, d, dtype=torch.float32, device=dev)
+        rc = None if res is None else _c(res).reshape(B * n, d)
+        d_attn = H.dropout_desc(p_attn, salt, dev) if (p_attn > 0 and mask is None) else None
+        d_out = H.dropout_desc(p_out, salt + 1, dev) if p_out > 0 else None
+        if kind in ("galerkin", "linear"):
+            attn_w, core = _galerkin_fwd(kind, Qp, Kp, Vp, out, rc, wf, bfc, (None, None), mask, d_attn, d_out, dims, sign,
+                                         n_kv=m)
+        elif kind == "softmax":
+            attn_w, core, ctx.flash = _softmax_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn, d_out, dims, sign, need_w)
+        else:
+            attn_w, core, (ctx.flash, ctx.f16, ctx.block16) = _fourier_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn,
+                                                                           d_out, dims, sign, need_w)
+        _save_named(ctx, wq=wq, gamma=gamma, x0=xcs[0], x1=xcs[1], x2=xcs[2], proj0=projs[0], proj1=projs[1],
+                    proj2=projs[2], st0=stats[0], st1=stats[1], st2=stats[2], t0=tiles[0], t1=tiles[1], t2=tiles[2],
+                    kvn_k=kvn_k, kvn_v=kvn_v, st_k=st_k, st_v=st_v, mask=mask, **core)
+        ctx.cfg, ctx.dims, ctx.n_kv, ctx.salt = cfg, dims, m, salt
+        ctx.has = (bqkv is not None, bfc is not None, res is not None)
+        attn_w = attn_w.detach()
+        ctx.mark_non_differentiable(attn_w)
+        return out.reshape(query.shape), attn_w
+
+    @staticmethod
+    def backward(ctx, gy, _gw):
+        (kind, h, norm_mask, eps, sign, p_attn, p_out, need_w, token_norm, share) = ctx.cfg
+        B, n, d, h, dk, p, Dr, DP = ctx.dims
+        m = ctx.n_kv
+        hbq, hbf, has_res = ctx.has
+        salt, dev = ctx.salt, gy.device
+        s = _saved(ctx)
+        s.out3, s.kvn = (s.t0, s.t1, s.t2), (s.kvn_k, s.kvn_v)      # what the cores read
+        g = _c(gy).reshape(B * n, d)
+        g_in = g                                             # unmasked: what flows to the residual branch
+        if p_out > 0:
+            g = H.dropout_apply(g, H.dropout_desc(p_out, salt + 1, dev))
+        d_attn = H.dropout_desc(p_attn, salt, dev) if (p_attn > 0 and s.mask is None) else None
+        if kind in ("galerkin", "linear"):
+            dO3, _, dwfc, dbfc = _galerkin_bwd(kind, s, g, d_attn, ctx.dims, sign, hbf, token_norm, False, False, n_kv=m)
+        elif kind == "softmax":
+            dO3, dwfc, dbfc = _softmax_bwd(s, g, d_attn, ctx.dims, sign, hbf, ctx.flash)
+        else:
+            dO3, dwfc, dbfc = _fourier_bwd(s, g, d_attn, ctx.dims, sign, hbf, ctx.flash, ctx.f16, ctx.block16)
+        dgamma = dbeta = None
+        if norm_mask:
+            dgamma = torch.empty(2, h, dk, dtype=torch.float32, device=dev)
+            dbeta = torch.empty(2, h, dk, dtype=torch.float32, device=dev)
+        if token_norm:
+            # dK', dV' -> gradients of the raw tiles, in place; the affine gradients in (norm_K, norm_V) order
+            H.token_norm_bwd(s.t1, dO3[1], s.gamma[0], s.st_k, B, m, h, dk, p, out=dO3[1], dgamma=dgamma[0], dbeta=dbeta[0])
+            H.token_norm_bwd(s.t2, dO3[2], s.gamma[1], s.st_v, B, m, h, dk, p, out=dO3[2], dgamma=dgamma[1], dbeta=dbeta[1])
+        rows = (B * n, B * m, B * m)
+        xcs, projs, stats = (s.x0, s.x1, s.x2), (s.proj0, s.proj1, s.proj2), (s.st0, s.st1, s.st2)
+        dwqkv = torch.empty(3 * d, d, dtype=torch.float32, device=dev)
+        dbqkv = torch.empty(3 * d, dtype=torch.float32, device=dev) if hbq else None
+        dxs = [None] * 3
+        for s0, ns in _CROSS_GROUPS[share]:
+            T, r0, r1 = rows[s0], s0 * d, (s0 + ns) * d
+            dproj = torch.empty(T, ns * d, dtype=torch.float32, device=dev)
+            for st in range(s0, s0 + ns):
+                ni = _stream_norm(st, norm_mask, token_norm)
+                col = (st - s0) * d
+                if ni is None:      # scatter only: the value columns of the gradient tile
+                    H.headtile_bwd(dO3[st], None, 0, None, None, T, h, dk, p, dproj[:, col:], ns * d)
+                else:
+                    H.headtile_bwd(dO3[st], projs[s0][:, col:], ns * d, s.gamma[ni], stats[st], T, h, dk, p, dproj[:, col:],
+                                   ns * d, dgamma[ni], dbeta[ni])
+            with H.side_branch(dev, T):     # weight gradient next to the data gradient
+                H.gemm(dproj, xcs[s0], dwqkv[r0:r1], ns * d, d, T, layout_a=1, layout_b=1, lda=ns * d, ldb=d, ldc=d,
+                       split_k=0, a_colsum=None if dbqkv is None else dbqkv[r0:r1])
+            dx = dxs[s0] = torch.empty(T, d, dtype=torch.float32, device=dev)
+            # (res is query: its gradient, the unmasked g_in, is folded into d(query) and the `res` slot returns None)
+            H.gemm(dproj, s.wq[r0:r1], dx, T, d, ns * d, layout_b=1, lda=ns * d, ldb=d, ldc=d,
+                   res=g_in if (has_res and s0 == 0) else None, ldr=d)
+            H.join_side(dev)
+        dq, dkey, dval = (None if t is None else t.reshape(B, -1, d) for t in dxs)
+        return (dq, dkey, dval, None, dwqkv, dbqkv, dgamma, dbeta, dwfc, dbfc, None, None, None)
+
+
+def cross_attention(query, key, value, pos, wqkv, bqkv, gamma, beta, wfc, bfc, *, kind: str, n_head: int, norm_mask: int,
+                    eps: float, res=None, sign: float = 1.0, p_out: float = 0.0, need_weights: bool = True,
+                    token_norm: bool = False):
+    """Attention block over query [B, n_q, d] and key, value [B, n_kv, d] that are not one tensor; ``res`` must be
+    ``query`` (or None).  Returns (out [B, n_q, d], attn_weight).  galerkin / linear: any n_q, n_kv (with ``pos`` they are
+    equal), M = (K'^T V') / n_q -- the sum over the n_kv memory tokens, the divisor the QUERY count (layers.py:719, 728).
+    fourier / softmax: n_q == n_kv, else NotImplementedError.  ``key is value`` and ``query is key`` are projected as one
+    product and their input receives one summed gradient.  The attention dropout modes act as in simple_attention."""
+    check_cross_shapes(query, key, value, pos)
+    _check_res_is_x(res, query, "cross_attention")
+    if kind in ("fourier", "softmax") and query.size(1) != key.size(1):
+        raise NotImplementedError(f"cross_attention: kind={kind!r} with n_q={query.size(1)} != n_kv={key.size(1)}: the fused "
+                                  "kernels take one token count")
+    if token_norm and key.size(1) < 2:       # nn.InstanceNorm1d: "Expected more than 1 spatial element when training"
+        raise ValueError(f"norm_type='instance' needs more than 1 token per sample to normalise over (got n_kv={key.size(1)})")
+    share = "kv" if key is value else ("qk" if query is key else "none")
+    mode = _attn_mode
+    mask, p_attn = None, 0.0
+    if mode == "reference":
+        p_attn = 0.5
+    elif mode == "replay":
+        if not _attn_masks:
+            raise RuntimeError("attention dropout mode 'replay' but no mask queued")
+        mk = _attn_masks.pop(0).to(device=query.device, dtype=torch.float32)
+        if kind in ("galerkin", "linear"):
+            Dr = mk.shape[-1]
+            DP = H.round4(Dr)
+            mask = torch.zeros(*mk.shape[:2], DP, DP, dtype=torch.float32, device=query.device)
+            mask[..., :Dr, :Dr] = mk
+        else:
+            mask = _c(mk)
+    cfg = (kind, int(n_head), int(norm_mask), float(eps), float(sign), float(p_attn), float(p_out),
+           bool(need_weights), bool(token_norm), share)
+    out, w = CrossAttentionFn.apply(query, key if share != "qk" else None, value if share != "kv" else None, pos, wqkv, bqkv,
+                                    gamma, beta, wfc, bfc, res, cfg, mask)
     return out, (w if w.numel() else None)

@@ -330,6 +330,20 @@ int gt_headnorm_bwd(const float* d_out, const float* qkv, const float* gamma, co
                     float* d_qkv, float* dgamma, float* dbeta, void* ws, int64_t ws_bytes,
                     void* stream);
 int64_t gt_headnorm_bwd_ws_bytes(int32_t T, int32_t h, int32_t dk);
+/* ABI v21, additive: the same for ONE stream with its own row count (cross-attention, where the query rows and the key /
+ * value rows differ).  X [T][ldx]: the h*dk value columns of one projection, e.g. the K or the V column block of a packed
+ * [T_kv][2d] product (ldx >= h*dk).  gamma, beta [h][dk]; gamma == NULL: no norm -- copy, coordinates and zero pad, stats
+ * untouched.  out [T][h][DP], stats [T][h][2] = (mean, rstd).  Backward: dX [T][lddx] receives the value columns only (the
+ * rest of a wider row is left alone); dgamma, dbeta [h][dk] through per-block partials in ws summed in block order
+ * (deterministic).  With gamma == NULL the backward is the scatter alone and X, stats, dgamma, dbeta, ws may be NULL.
+ * dk % 4 == 0 with ldx, lddx % 4 == 0 and 16-byte aligned operands moves float4; anything else runs the same kernels on
+ * scalars.  dk <= 256 and h * pow2(ceil(dk / 4)) <= 1024, else GT_ENOTSUP. */
+int gt_headtile_fwd(const float* X, int64_t ldx, const float* pos, const float* gamma, const float* beta, int32_t T,
+                    int32_t h, int32_t dk, int32_t p, float eps, float* out, float* stats, void* stream);
+int64_t gt_headtile_bwd_ws_bytes(int32_t T, int32_t h, int32_t dk);
+int gt_headtile_bwd(const float* d_out, const float* X, int64_t ldx, const float* gamma, const float* stats, int32_t T,
+                    int32_t h, int32_t dk, int32_t p, float* dX, int64_t lddx, float* dgamma, float* dbeta, void* ws,
+                    int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Galerkin attention core, small-matrix stage (layers.py:723-733 + :897 folded):

@@ -213,6 +213,12 @@ _PROTOS = {
     "gt_grad_sqnorm": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "gt_adam_clip_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_float, C.c_float, C.c_void_p] +
                           [C.c_float] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gt_h1loss2d_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "gt_h1loss2d_fwd": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_float, C.c_int32,
+                                                                                             C.c_void_p, C.c_int64, C.c_void_p]),
+    "gt_h1loss2d_final": (C.c_int, [C.c_int32] * 3 + [C.c_float] * 4 + [C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
+    "gt_h1loss2d_bwd": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + [C.c_int32] * 3 + [C.c_float] * 3 +
+                        [C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
@@ -1545,3 +1551,53 @@ def row_softmax_bwd(P, dPm, rows: int, n: int, mask, drop, dS=None, row0: int = 
         dS = torch.empty_like(P)
     _launch("gt_row_softmax_bwd", P, dPm, dS, rows, n, row0, mask, drop, nbytes=12.0 * P.numel())
     return dS
+
+
+# ----------------------------------------------------------------------------------- 2-D training objective
+def h1loss2d_pitch(P: torch.Tensor) -> Optional[int]:
+    """Pixel pitch (in floats) of an [N, n, n] tensor whose pixels are evenly spaced in memory -- a contiguous tensor (1) or
+    channel 0 of a contiguous [N, n, n, c] one (c); None for any other strides."""
+    N, n, n2 = P.shape
+    ld = P.stride(2)
+    ok = ld >= 1 and (P.stride(1) == n2 * ld or n == 1) and (P.stride(0) == n * n2 * ld or N == 1)
+    return ld if ok else None
+
+
+def h1loss2d_fwd(P: torch.Tensor, T: torch.Tensor, G: Optional[torch.Tensor], K: Optional[torch.Tensor], dilation: int,
+                 h: float, beta: float, gamma: float, eps: float, want_reg: bool):
+    """Per-sample terms of WeightedL2Loss2d (gt_h1loss2d_fwd + gt_h1loss2d_final).  P [N, n, n] with an even pixel pitch
+    (h1loss2d_pitch), T [N, n, n], G [N, n, n, 2] or None, K of N n n elements or None; T, G, K contiguous.  Returns
+    (loss [N], reg [N] or None, L2 [N], H1 [N])."""
+    need_f32_cuda(P, T, G, K)
+    N, n, _ = P.shape
+    ldp = h1loss2d_pitch(P)
+    if ldp is None or not (T.is_contiguous() and (G is None or G.is_contiguous()) and (K is None or K.is_contiguous())):
+        raise ValueError("h1loss2d_fwd: P needs evenly pitched pixels, T / G / K must be contiguous")
+    if T.shape != P.shape or (G is not None and G.shape != (N, n, n, 2)) or (K is not None and K.numel() != N * n * n):
+        raise ValueError("h1loss2d_fwd: T [N, n, n], G [N, n, n, 2], K of N n n elements expected")
+    out = torch.empty(4 if want_reg else 3, N, dtype=torch.float32, device=P.device)
+    loss, L2, H1, reg = out[0], out[1], out[2], (out[3] if want_reg else None)
+    wsb = lib().gt_h1loss2d_ws_bytes(N, n)
+    ws = workspace(P.device, max(16, wsb))
+    px = float(N) * n * n
+    _launch("gt_h1loss2d_fwd", P, ldp, T, G, K, N, n, int(dilation), float(h), int(bool(want_reg)), ws=ws,
+            nbytes=4.0 * px * (2 + (0 if G is None else 2) + (0 if K is None else 1)), shape=(N, n, ldp))
+    _launch("gt_h1loss2d_final", N, n, int(dilation), float(h), float(beta), float(gamma), float(eps), int(G is not None),
+            loss, reg, L2, H1, ws=ws, nbytes=float(wsb), shape=(N, n))
+    return loss, reg, L2, H1
+
+
+def h1loss2d_bwd(P: torch.Tensor, T: torch.Tensor, G: Optional[torch.Tensor], K: Optional[torch.Tensor], L2: torch.Tensor,
+                 H1: torch.Tensor, gl: Optional[torch.Tensor], gr: Optional[torch.Tensor], dilation: int, h: float,
+                 beta: float, gamma: float) -> torch.Tensor:
+    """dP [N, n, n] (dense) of h1loss2d_fwd from the upstream gradients gl, gr [N] of loss and reg (None = no gradient)."""
+    need_f32_cuda(P, T, G, K, L2, H1, gl, gr)
+    N, n, _ = P.shape
+    ldp = h1loss2d_pitch(P)
+    if ldp is None or not all(t is None or t.is_contiguous() for t in (T, G, K, L2, H1, gl, gr)):
+        raise ValueError("h1loss2d_bwd: P needs evenly pitched pixels, every other tensor must be contiguous")
+    dP = torch.empty(N, n, n, dtype=torch.float32, device=P.device)
+    px = float(N) * n * n
+    _launch("gt_h1loss2d_bwd", P, ldp, T, G, K, L2, H1, gl, gr, N, n, int(dilation), float(h), float(beta), float(gamma), dP,
+            nbytes=4.0 * px * (3 + (0 if G is None or gr is None else 2 + (0 if K is None else 1))), shape=(N, n, ldp))
+    return dP

@@ -1,7 +1,7 @@
 """Data containers, normaliser and losses with the reference's names (reference: libs/ft.py).
 
 These are host-side / few-kernels-per-step pieces outside the HIP hot path:
-they are plain PyTorch.  The ``.mat`` datasets of the reference are not redistributable; the
+they are plain PyTorch, except WeightedL2Loss2d.terms(), whose device float32 calls run on ops.weighted_l2_terms_2d.  The ``.mat`` datasets of the reference are not redistributable; the
 dataset classes load them when ``DATA_PATH`` provides the files and otherwise synthesise tensors
 of the same shapes (``synthetic=True``), which is what the benchmarks use.
 """
@@ -395,9 +395,44 @@ class WeightedL2Loss2d(_WeightedLoss):
         gy = (u[:, s:-s, d:] - u[:, s:-s, :-d]) / d
         return torch.stack([gx, gy], dim=-1) / h
 
+    def _hip_terms_ok(self, preds, targets, preds_prime=None, targets_prime=None, weights=None, K=None):
+        """Whether terms() takes the HIP operator (ops.weighted_l2_terms_2d) for this call.  Pure: reads is_cuda, dtype,
+        shape and requires_grad of its arguments and nothing else."""
+        if not (preds.is_cuda and preds.dtype == torch.float32 and preds.ndim == 3
+                and preds.shape[1] == preds.shape[2] and preds.shape[1] > self.dilation):
+            return False
+        if weights is not None or self.dim != 2 or not (preds_prime is None or self.alpha == 0):
+            return False
+        N, n, _ = preds.shape
+        if tuple(targets.shape) != (N, n, n):
+            return False
+        if targets_prime is not None and tuple(targets_prime.shape) != (N, n, n, 2):
+            return False
+        if K is not None and tuple(K.shape) not in ((N, n, n, 1), (N, n, n)):
+            return False
+        for t in (targets, targets_prime, K):
+            if t is not None and (t.requires_grad or not t.is_cuda or t.dtype != torch.float32):
+                return False
+        return True
+
     def terms(self, preds, targets, preds_prime=None, targets_prime=None, weights=None, K=None):
         """Per-sample relative errors without any host read-back (what a captured training step uses):
-        (loss [N], regulariser [N] or None, norms).  forward() reduces them and adds the metric."""
+        (loss [N], regulariser [N] or None, norms).  forward() reduces them and adds the metric.  Device float32 calls
+        without `weights` and without the alpha term run on the HIP operator, everything else on _terms_torch()."""
+        if not self._hip_terms_ok(preds, targets, preds_prime, targets_prime, weights, K):
+            return self._terms_torch(preds, targets, preds_prime, targets_prime, weights, K)
+        from .ops import weighted_l2_terms_2d
+        if self.noise > 0:
+            assert 0 <= self.noise <= 0.2
+            with torch.no_grad():
+                targets = targets * (1.0 + self.noise * torch.rand_like(targets))
+        loss, reg, L2, H1 = weighted_l2_terms_2d(
+            preds, targets, targets_prime, K if targets_prime is not None else None, dilation=self.dilation, h=self.h,
+            beta=self.beta, gamma=self.gamma, eps=self.eps, regularizer=self.regularizer)
+        return loss, reg, dict(L2=L2, H1=H1 if targets_prime is not None else 1)
+
+    def _terms_torch(self, preds, targets, preds_prime=None, targets_prime=None, weights=None, K=None):
+        """terms() in plain torch: the route of CPU tensors, `weights`, the alpha term and differentiable targets."""
         h = self.h if weights is None else weights
         d = self.dim
         K = torch.tensor(1) if K is None else K

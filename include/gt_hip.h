@@ -789,6 +789,39 @@ int gt_adam_clip_step(float* p, const float* g, float* m, float* v, int64_t n, c
                       float max_norm, const float* lr, float beta1, float beta2, float eps, float weight_decay,
                       const uint64_t* step, const float* beta1_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The 2-D training objective, per sample (ft.py:983-1105, WeightedL2Loss2d.forward without its alpha term and `weights`;
+ * ABI v21, additive).  P, T [N][n][n] prediction and target, G [N][n][n][2] target gradient (optional), K N n n coefficient
+ * values (optional, needs G; absent = 1).  Even dilation d < n, s = d / 2, m = n - d, M = n n:
+ *     A = sum T^2     E = sum (P - T)^2     Gs = sum_{i,j,c} K G_c^2
+ *     Dx P[i][j] = (P[i+s][j] - P[i-s][j]) / (d h),  Dy P[i][j] = (P[i][j+s] - P[i][j-s]) / (d h)   for s <= i, j < n - s
+ *     R  = sum over those (i, j) and c of (K[i][j] (G_c[i][j] - D_c P[i][j]))^2
+ *     L2 = A / M + eps      H1 = Gs / M + eps  (1 without G)
+ *     loss = beta (E / M) / L2      reg = gamma h (R / (2 m^2)) / H1
+ *   gt_h1loss2d_fwd    one streaming pass: per-block partial sums of (A, E, Gs, R) into ws.  want_reg == 0: R is not formed;
+ *                      G == NULL: Gs neither (want_reg != 0 then: GT_EINVAL)
+ *   gt_h1loss2d_final  merges the partials of each sample in block order, in double, and writes loss, L2, H1 [N] and, unless
+ *                      NULL, reg [N].  has_g: whether the forward had G.  Same N, n and ws as the forward, same stream
+ *   gt_h1loss2d_bwd    dP [N][n][n], dense, from the upstream gradients gl, gr [N] of loss and reg (either may be NULL = 0) and
+ *                      the L2, H1 the final pass wrote.  With r_c = K^2 (D_c P - G_c) on s <= i, j < n - s and 0 elsewhere:
+ *                        dP[i][j] = gl beta 2 / (M L2) (P - T)[i][j]
+ *                                 + gr gamma h 2 / (2 m^2 H1) / (d h) (r_x[i-s][j] - r_x[i+s][j] + r_y[i][j-s] - r_y[i][j+s])
+ *                      a gather: every pixel recomputes the at most four residuals it feeds
+ * P is read with the pixel pitch ldp >= 1 in floats (the callers pass channel 0 of an [N][n][n][c] tensor); T, G, K, dP are
+ * dense.  fp32 in every precision mode, the merge in double; no atomics: bit-identical from run to run.  The caller's
+ * stream, no allocation, no host read-back.  16-byte accesses where a tensor is 16-byte aligned (P: and ldp == 1), scalar
+ * ones otherwise.  n <= d, odd d, h <= 0, N < 1, K without G: GT_EINVAL; a pointer off a 4-byte (ws: 16-byte) boundary:
+ * GT_EALIGN; ws < gt_h1loss2d_ws_bytes(N, n): GT_EWS.
+ * ------------------------------------------------------------------------------------------- */
+int64_t gt_h1loss2d_ws_bytes(int32_t N, int32_t n);
+int gt_h1loss2d_fwd(const float* P, int64_t ldp, const float* T, const float* G, const float* K, int32_t N, int32_t n,
+                    int32_t dilation, float h, int32_t want_reg, void* ws, int64_t ws_bytes, void* stream);
+int gt_h1loss2d_final(int32_t N, int32_t n, int32_t dilation, float h, float beta, float gamma, float eps, int32_t has_g,
+                      float* loss, float* reg, float* L2, float* H1, const void* ws, int64_t ws_bytes, void* stream);
+int gt_h1loss2d_bwd(const float* P, int64_t ldp, const float* T, const float* G, const float* K, const float* L2,
+                    const float* H1, const float* gl, const float* gr, int32_t N, int32_t n, int32_t dilation, float h,
+                    float beta, float gamma, float* dP, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

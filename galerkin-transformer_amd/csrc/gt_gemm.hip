@@ -12,10 +12,9 @@
 // An XOR swizzle on the column index (bits 3-4, keyed by k>>2) makes both the transposing
 // ds_write_b32 of k-contiguous operands and the ds_read_b128 of the MFMA loop conflict-free.
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
+#include <type_traits>
 
 #include "gt_gemm_core.h"
 
@@ -419,35 +418,16 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ slabs, int nsplit
     }
 }
 
-struct Cfg { int mt, nt, wm, wn; };
-static const Cfg kCfgs[] = {{4, 4, 2, 2}, {2, 4, 2, 2}, {2, 2, 2, 2}, {2, 2, 4, 1}, {2, 1, 4, 1}};
-constexpr int kNumCfg = 5;
-
-template <int LA, int LB, int BK>
+// ---- launchers: f32_launch switches on the pick the descriptor layer (gt_gemm_desc.hip) made, f32_kernel_name prints it --------
+template <int LA, int LB, int BK, int HEAD>
 static void launch_cfg(int cfg, dim3 grid, hipStream_t st, const GemmP& p) {
     switch (cfg) {
-        case 0: hipLaunchKernelGGL((gemm_kernel<LA, LB, 4, 4, 2, 2, BK>), grid, dim3(256), 0, st, p); break;
-        case 1: hipLaunchKernelGGL((gemm_kernel<LA, LB, 2, 4, 2, 2, BK>), grid, dim3(256), 0, st, p); break;
-        case 2: hipLaunchKernelGGL((gemm_kernel<LA, LB, 2, 2, 2, 2, BK>), grid, dim3(256), 0, st, p); break;
-        case 3: hipLaunchKernelGGL((gemm_kernel<LA, LB, 2, 2, 4, 1, BK>), grid, dim3(256), 0, st, p); break;
-        default: hipLaunchKernelGGL((gemm_kernel<LA, LB, 2, 1, 4, 1, BK>), grid, dim3(256), 0, st, p); break;
+        case 0: hipLaunchKernelGGL((gemm_kernel<LA, LB, 4, 4, 2, 2, BK, HEAD>), grid, dim3(256), 0, st, p); break;
+        case 1: hipLaunchKernelGGL((gemm_kernel<LA, LB, 2, 4, 2, 2, BK, HEAD>), grid, dim3(256), 0, st, p); break;
+        case 2: hipLaunchKernelGGL((gemm_kernel<LA, LB, 2, 2, 2, 2, BK, HEAD>), grid, dim3(256), 0, st, p); break;
+        case 3: hipLaunchKernelGGL((gemm_kernel<LA, LB, 2, 2, 4, 1, BK, HEAD>), grid, dim3(256), 0, st, p); break;
+        default: hipLaunchKernelGGL((gemm_kernel<LA, LB, 2, 1, 4, 1, BK, HEAD>), grid, dim3(256), 0, st, p); break;
     }
-}
-
-// fused two-layer head: activations [tokens, K] times nn.Linear weight [N, K] only (LA = LB = 0)
-template <int NO>
-static void launch_head_no(int cfg, dim3 grid, hipStream_t st, const GemmP& p) {
-    switch (cfg) {
-        case 0: hipLaunchKernelGGL((gemm_kernel<0, 0, 4, 4, 2, 2, 16, NO>), grid, dim3(256), 0, st, p); break;
-        case 1: hipLaunchKernelGGL((gemm_kernel<0, 0, 2, 4, 2, 2, 16, NO>), grid, dim3(256), 0, st, p); break;
-        case 2: hipLaunchKernelGGL((gemm_kernel<0, 0, 2, 2, 2, 2, 16, NO>), grid, dim3(256), 0, st, p); break;
-        case 3: hipLaunchKernelGGL((gemm_kernel<0, 0, 2, 2, 4, 1, 16, NO>), grid, dim3(256), 0, st, p); break;
-        default: hipLaunchKernelGGL((gemm_kernel<0, 0, 2, 1, 4, 1, 16, NO>), grid, dim3(256), 0, st, p); break;
-    }
-}
-static void launch_head(int cfg, dim3 grid, hipStream_t st, const GemmP& p) {
-    if (p.n_out == 1) launch_head_no<1>(cfg, grid, st, p);
-    else launch_head_no<4>(cfg, grid, st, p);
 }
 
 static int num_cus() {
@@ -476,544 +456,65 @@ static void launch_stream(hipStream_t st, const GemmP& p) {
     int nblk = std::min(p.n_work, num_cus() * per_cu);
     if (const char* e = getenv("GT_GEMM_BLOCKS")) nblk = std::min(p.n_work, std::max(1, atoi(e)));
     nblk = ((nblk + 7) / 8) * 8;
-    GemmP q = p;
-    q.light_wait = 1;
-    if (const char* e = getenv("GT_GEMM_LIGHTWAIT")) q.light_wait = atoi(e) != 0;
-    if (getenv("GT_GEMM_DEBUG"))
-        fprintf(stderr, "[gt_gemm] stream<%d,%d,%d> M=%d N=%d K=%d work=%d per_cu=%d grid=%d\n", LA, LB, MT, p.M, p.N,
-                p.K, p.n_work, per_cu, nblk);
-    hipLaunchKernelGGL((gemm_stream_kernel<LA, LB, MT>), dim3(nblk), dim3(256), 0, st, q);
+    hipLaunchKernelGGL((gemm_stream_kernel<LA, LB, MT>), dim3(nblk), dim3(256), 0, st, p);
 }
 
-struct Plan { int cfg, bm, bn, bk, tiles_m, tiles_n, split, k_chunk, stream, x3; };
-
-static inline bool m4(int64_t v) { return (v & 3) == 0; }
-
-static bool has_epilogue(const gt_gemm_desc* d) {
-    return d->c_masked || d->bias || d->rp || d->add || d->pre || d->act || d->aux_op || d->drop.p > 0.f || d->res ||
-           d->out_scale != 1.f || d->ep_mode != GT_EP_NORMAL || d->K2 > 0;
+// f(LA, LB) with the two layouts as compile-time constants
+template <class F>
+static void with_layouts(int la, int lb, F&& f) {
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    if (la == 0 && lb == 0) f(I0{}, I0{});
+    else if (la == 0) f(I0{}, I1{});
+    else if (lb == 0) f(I1{}, I0{});
+    else f(I1{}, I1{});
 }
 
-// number of bf16 planes the split-operand kernels (gt_x3_core.h) would use for d, 0 = fp32 MFMA kernels
-static int x3_planes(const gt_gemm_desc* d) {
-    // GT_PREC_F16X2: the packed-B kernels run the two-term fp16 arithmetic, every other split-operand launch bf16x3
-    const int planes = (d->precision == GT_PREC_BF16X3 || d->precision == GT_PREC_F16X2) ? 3
-                       : d->precision == GT_PREC_BF16X2 ? 2 : d->precision == GT_PREC_BF16 ? 1 : 0;
-    if (!planes || !x3_shape_ok(d) || (d->a_colsum && d->layout_a != 1)) return 0;
-    return planes;
-}
-
-static int make_plan(const gt_gemm_desc* d, Plan* pl) {
-    if (d->M <= 0 || d->N <= 0 || d->K < 0 || d->batch0 <= 0 || d->batch1 <= 0) return GT_EINVAL;
-    if (d->precision < GT_PREC_F32 || d->precision > GT_PREC_F16X2) return GT_EINVAL;
-    if (d->act < GT_ACT_NONE || (d->act > GT_ACT_SILU && d->act != GT_ACT_DROP_SILU && d->act != GT_ACT_SILU2))
-        return GT_EINVAL;                          // GT_ACT_GELU: elementwise entry points only
-    if (d->act == GT_ACT_SILU2 && d->drop.p > 0.f) return GT_EINVAL;
-    const int64_t batch = (int64_t)d->batch0 * d->batch1;
-    if (batch > 65535) return GT_EINVAL;
-    pl->x3 = x3_planes(d);
-    // Tile choice by a small cost model (calibrated on MI355X with tools/gemm_probe.py): the blocks that
-    // share a CU share its matrix pipes, so time ~ ceil(tiles / CUs) * tile area / efficiency of the
-    // configuration (MFMAs per LDS read / per barrier).  Padding waste shows up through the tile count.
-    static const double kEff[kNumCfg] = {1.00, 0.95, 0.80, 0.70, 0.45};
-    int c = 0;
-    double best = 0.0;
-    for (int i = 0; i < kNumCfg; ++i) {
-        const int bm = kCfgs[i].wm * 16 * kCfgs[i].mt, bn = kCfgs[i].wn * 16 * kCfgs[i].nt;
-        const bool head_ep = d->ep_mode == GT_EP_ROWDOT || d->ep_mode == GT_EP_MLP_BWD;
-        if (head_ep && bn < d->N) continue;                         // the fused head needs whole rows per block
-        // the 128x128 head instance needs > 256 registers (one block per CU): the 64x128 one runs two
-        if (head_ep && i == 0 && d->N <= 128) continue;
-        const double tiles = (double)ceil_div(d->M, bm) * ceil_div(d->N, bn) * (double)batch;
-        // under-filled grids: with split-K available the K-slices fill the chip (time ~ total padded work),
-        // otherwise every block has a CU to itself (time ~ one tile)
-        const bool can_split = d->split_k != 1 && d->K >= 512 && !has_epilogue(d);
-        const double units = tiles >= 256.0 ? std::ceil(tiles / 256.0) : (can_split ? tiles / 256.0 : 1.0);
-        const double cost = units * bm * bn / kEff[i];
-        if (best == 0.0 || cost < best) { best = cost; c = i; }
-    }
-    if (const char* e = getenv("GT_GEMM_CFG")) {      // tuning/debug override (tools/gemm_bench.py)
-        const int f = atoi(e);
-        if (f >= 0 && f < kNumCfg) c = f;
-    }
-    if (pl->x3) c = 0;                                // the split-operand kernel has one geometry: 128 x 128 tiles
-    pl->cfg = c;
-    // BK=32 pays for the long-K reductions with row-contiguous operands (weight gradients); the
-    // short-K token GEMMs are prologue/epilogue-bound and run better with the smaller stage
-    pl->bk = (d->layout_a == 1 && d->layout_b == 1 && d->K >= 512) ? 32 : 16;
-    if (const char* e = getenv("GT_GEMM_BK")) pl->bk = (atoi(e) == 16) ? 16 : 32;
-    // streamed kernel: 128-wide N tiles, 16-byte aligned operands, whole granules at every edge
-    // (measured: it wins from K = 256 up; at K = 128 a tile is only 4 stages long and the v1 kernel's
-    // higher occupancy hides the per-tile epilogue better)
-    pl->stream = (c <= 1) && d->K >= 256 && (d->K & 3) == 0 && !misaligned16(d->A, d->B) && m4(d->lda) &&
-                 m4(d->ldb) && m4(d->a_bs0) && m4(d->a_bs1) && m4(d->b_bs0) && m4(d->b_bs1) &&
-                 (d->layout_a == 0 || (d->M & 3) == 0) && (d->layout_b == 0 || (d->N & 3) == 0);
-    if (const char* e = getenv("GT_GEMM_STREAM")) pl->stream = pl->stream && atoi(e) != 0;
-    if (d->ep_mode != GT_EP_NORMAL) { pl->stream = 0; pl->bk = 16; }
-    if (d->K2 > 0) pl->stream = 0;
-    if (pl->stream) pl->bk = 32;
-    if (pl->x3) { pl->stream = 0; pl->bk = 16; }
-    pl->bm = kCfgs[c].wm * 16 * kCfgs[c].mt;
-    pl->bn = kCfgs[c].wn * 16 * kCfgs[c].nt;
-    pl->tiles_m = ceil_div(d->M, pl->bm);
-    pl->tiles_n = ceil_div(d->N, pl->bn);
-    const int64_t blocks = (int64_t)pl->tiles_m * pl->tiles_n * batch;
-    int split = d->split_k;
-    if (split == 0) {
-        split = 1;
-        // aim at ~2 resident blocks per CU (two waves per SIMD hide each other's barriers and loads)
-        int target = 512;
-        if (const char* e = getenv("GT_GEMM_TARGET")) target = std::max(1, atoi(e));
-        if (!has_epilogue(d) && blocks < 384 && d->K >= 512) {
-            split = (int)std::min<int64_t>((target + blocks / 2) / blocks, d->K / (4 * pl->bk));
-            if (split < 1) split = 1;
-            // token-contracted products on the split engine hand whole groups of K chunks to the eight XCDs (gemm_x3w_kernel's
-            // chunk-major grid): a multiple of eight chunks keeps every XCD at or under its 64 resident blocks -- 171 chunks x
-            // 3 tiles put 66 on seven of them and the launch paid a second round (178 us against 117)
-            if (pl->x3 && d->layout_a == 1 && d->layout_b == 1 && split >= 16) split &= ~7;
-        }
-    }
-    if (d->cv_c > 0 && d->cv_wgrad)                   // nine taps per chunk: ~3 resident blocks per CU, whole XCD groups
-        split = (int)std::max<int64_t>(1, std::min<int64_t>((768 + blocks - 1) / blocks, d->K / (4 * pl->bk)));
-    if (split > 1 && has_epilogue(d)) return GT_ENOTSUP;
-    if (split > 1024) split = 1024;
-    int chunk = ceil_div(std::max(d->K, 1), split);
-    chunk = ((chunk + pl->bk - 1) / pl->bk) * pl->bk;
-    split = std::max(1, ceil_div(std::max(d->K, 1), chunk));
-    pl->split = split;
-    pl->k_chunk = chunk;
-    return 0;
-}
-
-
-}  // namespace gt
-
-using namespace gt;
-
-// GT_EP_HEADNORM with 48-wide heads (ex3: d_model 192, 4 heads): the fused epilogue needs every head inside one wave's 64
-// output columns, so the product runs with each head in a 64-column SLOT -- N' = 3 h 64 tile columns, the 16 columns behind a
-// head are zero rows of the PACKED weight (the pack kernels map slot rows to weight rows; the weight itself is read in place),
-// and the epilogue normalises / stores the 48 real columns.  The caller's descriptor keeps N = 3 h 48; every entry point
-// plans with this copy.  (A third more MFMA work in a launch that is bound by its memory traffic; no extra HBM byte.)
-static const gt_gemm_desc* hn_slots(const gt_gemm_desc* d, gt_gemm_desc* tmp) {
-    if (!d || d->ep_mode != GT_EP_HEADNORM || d->hn_dk != 48 || d->hn_h <= 0 || d->N != 3 * d->hn_h * 48) return d;
-    *tmp = *d;
-    tmp->N = 3 * d->hn_h * 64;
-    return tmp;
-}
-
-extern "C" void gt_gemm_desc_init(gt_gemm_desc* d) {
-    memset(d, 0, sizeof(*d));
-    d->alpha = 1.f;
-    d->out_scale = 1.f;
-    d->a_drop_sign = 1.f;
-    d->aux_scale = 1.f;
-    d->batch0 = d->batch1 = 1;
-    d->split_k = 1;
-}
-
-extern "C" int gt_gemm_plan(const gt_gemm_desc* d, int32_t* bm, int32_t* bn, int32_t* split) {
-    Plan pl;
-    gt_gemm_desc hs;
-    d = hn_slots(d, &hs);
-    int rc = make_plan(d, &pl);
-    if (rc) return rc;
-    if (bm) *bm = pl.bm;
-    if (bn) *bn = pl.bn;
-    if (split) *split = pl.split;
-    return 0;
-}
-
-static int64_t slab_bytes(const gt_gemm_desc* d, const Plan& pl) {
-    if (pl.split <= 1) return 0;
-    return (int64_t)pl.split * d->batch0 * d->batch1 * d->M * d->N * (int64_t)sizeof(float);
-}
-static int64_t acs_parts(const gt_gemm_desc* d, const Plan& pl) {
-    return d->a_colsum ? (int64_t)pl.split * d->batch0 * d->batch1 : 0;
-}
-
-// Symbol of the kernel instance gt_gemm would launch for `d` (as rocprofv3 prints it), for matching the
-// bench's roofline line against a kernel trace.
-extern "C" int gt_gemm_kernel_name(const gt_gemm_desc* d, char* buf, int32_t n) {
-    Plan pl;
-    if (!d || !buf || n <= 0) return GT_EINVAL;
-    gt_gemm_desc hs;
-    d = hn_slots(d, &hs);
-    if (!getenv("GT_GEMM_NO_TSMM") && tsmm_eligible(d)) {
-        snprintf(buf, n, "%s", tsmm_kernel_name(d));
-        return 0;
-    }
-    int rc = make_plan(d, &pl);
-    if (rc) return rc;
-    const Cfg& c = kCfgs[pl.cfg];
-    if (pl.x3) {
-        GemmP q;
-        memset(&q, 0, sizeof(q));
-        q.M = d->M; q.N = d->N; q.K = d->K; q.K2 = d->K2; q.cv_C = d->cv_c; q.cv_wgrad = d->cv_wgrad != 0;
-        if (x3_packed_ok(d, pl.x3, pl.split)) { q.Bp = d->B; q.bp_f16 = d->precision == GT_PREC_F16X2; }
-        q.wg_f16 = x3w_ok(d, pl.split);
-        q.a_vec = !misaligned16(d->A) && m4(d->lda) && m4(d->a_bs0) && m4(d->a_bs1);
-        q.b_vec = !misaligned16(d->B) && m4(d->ldb) && m4(d->b_bs0) && m4(d->b_bs1);
-        snprintf(buf, n, "%s", x3_kernel_name(q, d->layout_a, d->layout_b, pl.x3,
-                                              d->ep_mode == GT_EP_HEADNORM ? hn_slot_width(d->hn_dk) : 0));
-    }
-    else if (pl.stream)
-        snprintf(buf, n, "void gt::gemm_stream_kernel<%d, %d, %d>(gt::GemmP)", d->layout_a, d->layout_b, c.mt);
-    else
-        snprintf(buf, n, "void gt::gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %d>(gt::GemmP)", d->layout_a, d->layout_b,
-                 c.mt, c.nt, c.wm, c.wn, pl.bk,
-                 d->ep_mode == GT_EP_NORMAL ? 0 : (d->n_out == 1 ? 1 : 4));
-    return 0;
-}
-
-static bool width_split(const gt_gemm_desc* d, gt_gemm_desc* a, gt_gemm_desc* b);
-static int64_t ws_bytes_one(const gt_gemm_desc* d);
-
-extern "C" int64_t gt_gemm_ws_bytes(const gt_gemm_desc* d) {
-    gt_gemm_desc a, b, hs;
-    d = hn_slots(d, &hs);
-    if (d && width_split(d, &a, &b)) return std::max(ws_bytes_one(&a), ws_bytes_one(&b));     // (b_packed is inherited by both)
-    return ws_bytes_one(d);
-}
-
-static int64_t ws_bytes_one(const gt_gemm_desc* d) {
-    Plan pl;
-    if (d && !getenv("GT_GEMM_NO_TSMM") && tsmm_eligible(d)) return tsmm_ws_bytes(d);
-    if (make_plan(d, &pl)) return 0;
-    if (pl.x3 && x3_packed_ok(d, pl.x3, pl.split)) return d->b_packed ? 0 : x3_packed_bytes(d);
-    const int64_t parts = acs_parts(d, pl);
-    if (d->ep_mode == GT_EP_MLP_BWD)
-        return (int64_t)pl.tiles_m * kCfgs[pl.cfg].wm * d->n_out * d->N * (int64_t)sizeof(float);
-    return slab_bytes(d, pl) + (parts > 0 ? parts * d->M * (int64_t)sizeof(float) : 0);
-}
-
-// One kernel launch (+ split-K reduce) for the column range [n_off, n_off + d->N) of a problem whose
-// full width is drop_ld (d already points at that column range).
-static int gemm_one(const gt_gemm_desc* d, int drop_ld, int n_off, void* ws, int64_t ws_bytes, void* stream) {
-    if (!d || !d->A || !d->B) return GT_EINVAL;
-    if (!d->C && d->ep_mode != GT_EP_ROWDOT && !(d->ep_mode == GT_EP_HEADNORM && (d->hn_skip_raw_mask & 7) == 7))
-        return GT_EINVAL;
-    if (d->ep_mode == GT_EP_HEADNORM) {
-        if (d->layout_a || d->layout_b || d->batch0 * d->batch1 != 1 || d->K2 > 0 || d->split_k > 1) return GT_ENOTSUP;
-        if (d->hn_h <= 0 || d->hn_p < 0 || d->N != 3 * d->hn_h * hn_slot_width(d->hn_dk) || (d->hn_norm_mask & ~7)) return GT_EINVAL;
-        if (!d->hn_out || (d->hn_p > 0 && !d->hn_pos)) return GT_EINVAL;
-        if (d->hn_norm_mask && (!d->hn_gamma || !d->hn_beta || !d->hn_stats)) return GT_EINVAL;
-        if (d->rp || d->add || d->pre || d->act || d->aux_op || d->drop.p > 0.f || d->res || d->out_scale != 1.f ||
-            d->a_drop.p > 0.f || d->a_colsum)
-            return GT_ENOTSUP;
-    } else if (d->ep_mode != GT_EP_NORMAL) {
-        if (d->ep_mode != GT_EP_ROWDOT && d->ep_mode != GT_EP_MLP_BWD) return GT_EINVAL;
-        if (d->N > 128 || d->batch0 * d->batch1 != 1 || d->n_out < 1 || d->n_out > 4 || !d->w2) return GT_ENOTSUP;
-        if (d->ep_mode == GT_EP_ROWDOT && !d->out2) return GT_EINVAL;
-        if (d->ep_mode == GT_EP_MLP_BWD && (!d->g2 || !d->dw2)) return GT_EINVAL;
-        if (d->a_colsum || d->a_drop.p > 0.f) return GT_ENOTSUP;
-    }
-    if ((d->layout_a | d->layout_b) & ~1) return GT_EINVAL;
-    if (d->cv_c != 0) {                               // implicit 3x3 convolution on A (gt_hip.h: cv_*)
-        if (d->cv_c < 0 || d->cv_h <= 0 || d->cv_w <= 0) return GT_EINVAL;
-        if (d->cv_wgrad) {
-            if (d->K % ((int64_t)d->cv_h * d->cv_w) != 0 || d->N != d->cv_c || d->batch0 != 9 || d->batch1 != 1)
-                return GT_EINVAL;
-            if (d->layout_a != 1 || d->layout_b != 1 || d->split_k != 0 || d->cv_w < 16 || has_epilogue(d) ||
-                d->a_drop.p > 0.f || d->a_colsum)
-                return GT_ENOTSUP;
-        } else {
-            if (d->K != 9 * d->cv_c || d->M % ((int64_t)d->cv_h * d->cv_w) != 0) return GT_EINVAL;
-            if (d->layout_a || d->layout_b || (d->cv_c & 15) || d->batch0 * d->batch1 != 1 || d->split_k != 1 ||
-                d->a_drop.p > 0.f || d->a_colsum || d->K2 > 0 || d->ep_mode != GT_EP_NORMAL)
-                return GT_ENOTSUP;
-        }
-    }
-    if (d->C && !getenv("GT_GEMM_NO_TSMM") && tsmm_eligible(d)) return d->b_packed ? GT_EINVAL : tsmm_run(d, ws, ws_bytes, stream);
-    if (d->rp < 0 || d->rp > 8) return GT_EINVAL;
-    if ((d->a_drop.p > 0.f && !d->a_drop.seed) || (d->drop.p > 0.f && !d->drop.seed)) return GT_EINVAL;
-    if (d->a_drop.p >= 1.f || d->drop.p >= 1.f || d->a_drop.p < 0.f || d->drop.p < 0.f) return GT_EINVAL;
-    Plan pl;
-    int rc = make_plan(d, &pl);
-    if (rc) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int64_t batch = (int64_t)d->batch0 * d->batch1;
-
-    GemmP p;
-    memset(&p, 0, sizeof(p));
-    p.M = d->M; p.N = d->N; p.K = d->K;
-    p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n; p.batch1 = d->batch1; p.k_chunk = pl.k_chunk;
-    p.n_split = pl.split; p.n_batch = (int)batch;
-    const int64_t n_work64 = (int64_t)pl.tiles_m * pl.tiles_n * pl.split * batch;
-    if (n_work64 > (1 << 30)) return GT_EINVAL;
-    p.n_work = (int)n_work64;
-    p.A = d->A; p.lda = d->lda; p.a_bs0 = d->a_bs0; p.a_bs1 = d->a_bs1;
-    p.B = d->B; p.ldb = d->ldb; p.b_bs0 = d->b_bs0; p.b_bs1 = d->b_bs1;
-    p.a_vec = !misaligned16(d->A) && m4(d->lda) && m4(d->a_bs0) && m4(d->a_bs1);
-    p.b_vec = !misaligned16(d->B) && m4(d->ldb) && m4(d->b_bs0) && m4(d->b_bs1);
-    p.a_drop = make_drop(&d->a_drop, d->a_drop_sign);
-    p.a_drop_ld = d->a_drop_ld; p.a_drop_bstride = d->a_drop_bstride;
-    if (d->cv_c > 0) {
-        if (!pl.x3 || (!d->cv_wgrad && pl.split != 1)) return GT_ENOTSUP;
-        p.cv_H = d->cv_h; p.cv_W = d->cv_w; p.cv_C = d->cv_c; p.cv_wgrad = d->cv_wgrad != 0;
-        // lda (forward / data gradient) / ldb (weight gradient) = the pixel pitch of the image: >= cv_c, so a convolution can
-        // read a channel slice of a wider channels-last buffer in place (values below cv_c mean "dense")
-        if (d->cv_wgrad) {
-            p.ldb = d->ldb > d->cv_c ? d->ldb : d->cv_c; p.b_bs0 = p.b_bs1 = 0;
-            p.b_vec = !misaligned16(d->B) && m4(p.ldb);
-        } else {
-            p.lda = d->lda > d->cv_c ? d->lda : d->cv_c;
-            p.a_vec = !misaligned16(d->A) && m4(p.lda);
-        }
-    }
-
-    if (d->K2 > 0) {
-        if (!d->A2 || !d->B2 || d->a_drop.p > 0.f || d->a_colsum || pl.split != 1) return GT_ENOTSUP;
-        p.K2 = d->K2; p.A2 = d->A2; p.lda2 = d->lda2; p.a2_bs0 = d->a2_bs0; p.a2_bs1 = d->a2_bs1;
-        p.B2 = d->B2; p.ldb2 = d->ldb2; p.b2_bs0 = d->b2_bs0; p.b2_bs1 = d->b2_bs1;
-        p.a2_vec = !misaligned16(d->A2) && m4(d->lda2) && m4(d->a2_bs0) && m4(d->a2_bs1);
-        p.b2_vec = !misaligned16(d->B2) && m4(d->ldb2) && m4(d->b2_bs0) && m4(d->b2_bs1);
-    }
-    const int64_t mn = (int64_t)d->M * d->N;
-    float* dw2_partial = nullptr;
-    const int dw2_slabs = pl.tiles_m * kCfgs[pl.cfg].wm;
-    if (d->ep_mode == GT_EP_HEADNORM) {
-        if (!pl.x3 || pl.split != 1) return GT_ENOTSUP;
-        p.ep_mode = d->ep_mode;
-        p.hn_gamma = d->hn_gamma; p.hn_beta = d->hn_beta; p.hn_pos = d->hn_pos; p.hn_out = d->hn_out;
-        p.hn_stats = d->hn_stats; p.hn_h = d->hn_h; p.hn_dk = hn_slot_width(d->hn_dk); p.hn_dkr = d->hn_dk; p.hn_p = d->hn_p;
-        p.hn_DP = (d->hn_dk + d->hn_p + 3) & ~3; p.hn_mask = d->hn_norm_mask; p.hn_eps = d->hn_eps;
-        p.hn_skip_raw = d->hn_skip_raw_mask & 7; p.hn_plain = d->hn_plain != 0;
-    } else if (d->ep_mode != GT_EP_NORMAL) {
-        if (pl.tiles_n != 1 || pl.split != 1) return GT_ENOTSUP;
-        p.ep_mode = d->ep_mode; p.n_out = d->n_out; p.w2 = d->w2; p.ldw2 = d->ldw2; p.b2 = d->b2;
-        p.out2 = d->out2; p.g2 = d->g2;
-        if (d->ep_mode == GT_EP_MLP_BWD) {
-            const int64_t need = (int64_t)dw2_slabs * d->n_out * d->N * (int64_t)sizeof(float);
-            if (!ws || ws_bytes < need) return GT_EWS;
-            dw2_partial = reinterpret_cast<float*>(ws);
-            p.dw2_partial = dw2_partial;
-        }
-    }
-    const int64_t parts = acs_parts(d, pl);
-    float* acs_partial = nullptr;
-    if (d->a_colsum) {
-        if (d->layout_a != 1) return GT_ENOTSUP;
-        // without a mask the sign of a_drop_sign is not applied by the loader: fold it into the reduce
-        const bool need_scale = !(d->a_drop.p > 0.f) && d->a_drop_sign != 1.f;
-        if (parts > 1 || need_scale) {
-            const int64_t off = slab_bytes(d, pl);
-            if (!ws || ws_bytes < off + parts * d->M * (int64_t)sizeof(float)) return GT_EWS;
-            acs_partial = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + off);
-            p.acs = acs_partial;
-        } else {
-            p.acs = d->a_colsum;
-        }
-    }
-    if (pl.split > 1) {
-        const int64_t need = (int64_t)pl.split * batch * mn * (int64_t)sizeof(float);
-        if (!ws || ws_bytes < need) return GT_EWS;
-        p.C = reinterpret_cast<float*>(ws);
-        p.ldc = d->N; p.c_bs0 = (int64_t)d->batch1 * mn; p.c_bs1 = mn; p.c_split = batch * mn;
-        p.c_vec = !misaligned16(ws) && m4(d->N) && m4(mn);
-        p.raw = 1;
-        p.alpha = 1.f; p.out_scale = 1.f;
+int f32_launch(const GemmP& p, const F32Pick& k, dim3 grid, hipStream_t st) {
+    if (k.family == F32_HEAD) {     // fused two-layer head: activations [tokens, K] times nn.Linear weight [N, K] only
+        if (k.LA || k.LB) return GT_ENOTSUP;
+        if (k.n_out == 1) launch_cfg<0, 0, 16, 1>(k.cfg, grid, st, p);
+        else launch_cfg<0, 0, 16, 4>(k.cfg, grid, st, p);
     } else {
-        p.C = d->C; p.ldc = d->ldc; p.c_bs0 = d->c_bs0; p.c_bs1 = d->c_bs1; p.c_split = 0;
-        p.c_vec = !misaligned16(d->C) && m4(d->ldc) && m4(d->c_bs0) && m4(d->c_bs1);
-        if (d->res) p.c_vec = p.c_vec && !misaligned16(d->res) && m4(d->ldr) && m4(d->r_bs0) && m4(d->r_bs1);
-        if (d->add) p.c_vec = p.c_vec && !misaligned16(d->add) && m4(d->ldadd) && m4(d->add_bs0) && m4(d->add_bs1);
-        if (d->aux_op) p.c_vec = p.c_vec && !misaligned16(d->aux) && m4(d->ldaux) && m4(d->aux_bs0) && m4(d->aux_bs1);
-        if (d->pre) p.c_vec = p.c_vec && !misaligned16(d->pre) && m4(d->ldpre) && m4((int64_t)d->M * d->ldpre);
-        p.alpha = d->alpha; p.bias = d->bias;
-        p.rp = d->rp; p.rp_a = d->rp_a; p.rp_lda = d->rp_lda; p.rp_a_bs0 = d->rp_a_bs0;
-        p.rp_b = d->rp_b; p.rp_ldb = d->rp_ldb;
-        if (p.rp && (!p.rp_a || !p.rp_b)) return GT_EINVAL;
-        p.add = d->add; p.ldadd = d->ldadd; p.add_bs0 = d->add_bs0; p.add_bs1 = d->add_bs1;
-        p.pre = d->pre; p.ldpre = d->ldpre;
-        p.act = d->act; p.aux_op = d->aux_op; p.aux = d->aux; p.ldaux = d->ldaux;
-        p.aux_bs0 = d->aux_bs0; p.aux_bs1 = d->aux_bs1; p.aux_scale = d->aux_scale;
-        if (p.aux_op && !p.aux) return GT_EINVAL;
-        p.drop = make_drop(&d->drop);
-        p.drop_ld = drop_ld; p.n_off = n_off;
-        p.res = d->res; p.ldr = d->ldr; p.r_bs0 = d->r_bs0; p.r_bs1 = d->r_bs1;
-        p.out_scale = d->out_scale;
-        if (d->c_masked) {
-            if (batch != 1 || d->ep_mode != GT_EP_NORMAL || d->K2 > 0) return GT_ENOTSUP;
-            if (d->c_mask.p < 0.f || d->c_mask.p >= 1.f || (d->c_mask.p > 0.f && !d->c_mask.seed)) return GT_EINVAL;
-            p.c2 = d->c_masked; p.ldc2 = d->ldc_masked; p.drop2 = make_drop(&d->c_mask);
-            p.c_vec = p.c_vec && !misaligned16(d->c_masked) && m4(d->ldc_masked);
-        }
-    }
-    if (d->c_masked && pl.split > 1) return GT_ENOTSUP;
-
-    dim3 grid((unsigned)(pl.tiles_m * pl.tiles_n), (unsigned)pl.split, (unsigned)batch);
-    const int lay = d->layout_a * 2 + d->layout_b;
-    if (d->b_packed && !(pl.x3 && x3_packed_ok(d, pl.x3, pl.split))) return GT_EINVAL;   // not a packed-B launch: see gt_hip.h
-    if (pl.x3) {
-        if (x3_packed_ok(d, pl.x3, pl.split)) {
-            int rcp = x3_pack_b(d, p, ws, ws_bytes, st);
-            if (rcp) return rcp;
-        }
-        p.wg_f16 = x3w_ok(d, pl.split);
-        int rcx = x3_launch(p, d->layout_a, d->layout_b, pl.x3, (unsigned)(pl.tiles_m * pl.tiles_n), (unsigned)pl.split,
-                            (unsigned)batch, st);
-        if (rcx) return rcx;
-    } else if (d->ep_mode != GT_EP_NORMAL) {
-        if (lay != 0) return GT_ENOTSUP;
-        launch_head(pl.cfg, grid, st, p);
-    } else if (pl.stream) {
-        if (pl.cfg == 0) {
-            if (lay == 0) launch_stream<0, 0, 4>(st, p);
-            else if (lay == 1) launch_stream<0, 1, 4>(st, p);
-            else if (lay == 2) launch_stream<1, 0, 4>(st, p);
-            else launch_stream<1, 1, 4>(st, p);
-        } else {
-            if (lay == 0) launch_stream<0, 0, 2>(st, p);
-            else if (lay == 1) launch_stream<0, 1, 2>(st, p);
-            else if (lay == 2) launch_stream<1, 0, 2>(st, p);
-            else launch_stream<1, 1, 2>(st, p);
-        }
-    } else if (pl.bk == 32) {
-        if (lay == 0) launch_cfg<0, 0, 32>(pl.cfg, grid, st, p);
-        else if (lay == 1) launch_cfg<0, 1, 32>(pl.cfg, grid, st, p);
-        else if (lay == 2) launch_cfg<1, 0, 32>(pl.cfg, grid, st, p);
-        else launch_cfg<1, 1, 32>(pl.cfg, grid, st, p);
-    } else {
-        if (lay == 0) launch_cfg<0, 0, 16>(pl.cfg, grid, st, p);
-        else if (lay == 1) launch_cfg<0, 1, 16>(pl.cfg, grid, st, p);
-        else if (lay == 2) launch_cfg<1, 0, 16>(pl.cfg, grid, st, p);
-        else launch_cfg<1, 1, 16>(pl.cfg, grid, st, p);
+        with_layouts(k.LA, k.LB, [&](auto la, auto lb) {
+            constexpr int LA = decltype(la)::value, LB = decltype(lb)::value;
+            if (k.family == F32_STREAM && k.cfg == 0) launch_stream<LA, LB, 4>(st, p);
+            else if (k.family == F32_STREAM) launch_stream<LA, LB, 2>(st, p);
+            else if (k.BK == 32) launch_cfg<LA, LB, 32, 0>(k.cfg, grid, st, p);
+            else launch_cfg<LA, LB, 16, 0>(k.cfg, grid, st, p);
+        });
     }
     GT_LAUNCH_CHECK();
-    if (dw2_partial) {
-        const int64_t n2 = (int64_t)d->n_out * d->N;
-        int rc3 = gt_slab_reduce(dw2_partial, n2, dw2_slabs, n2, 1.f, d->dw2, stream);
-        if (rc3) return rc3;
-    }
-    if (acs_partial) {
-        const float sc = (d->a_drop.p > 0.f) ? 1.f : d->a_drop_sign;
-        int rc2 = gt_slab_reduce(acs_partial, d->M, (int)parts, d->M, sc, d->a_colsum, stream);
-        if (rc2) return rc2;
-    }
+    return 0;
+}
 
-    if (pl.split > 1) {
-        const int64_t total = batch * mn;
-        const bool v4 = m4(d->N) && m4(d->ldc) && m4(d->c_bs0) && m4(d->c_bs1) && !misaligned16(d->C, ws);
-        if (v4) {
-            const int64_t total4 = total / 4;
-            const int blocks4 = (int)((total4 + 31) / 32);
-            hipLaunchKernelGGL(splitk_reduce4_kernel, dim3(blocks4), dim3(256), 0, st,
-                               reinterpret_cast<const float*>(ws), pl.split, batch * mn, d->M, d->N / 4,
-                               d->batch1, d->alpha, d->C, d->ldc, d->c_bs0, d->c_bs1, total4);
-            GT_LAUNCH_CHECK();
-            return 0;
-        }
+const char* f32_kernel_name(const F32Pick& k) {
+    static thread_local char buf[112];
+    const F32Cfg& c = kF32Cfgs[k.cfg];
+    if (k.family == F32_STREAM)
+        snprintf(buf, sizeof(buf), "void gt::gemm_stream_kernel<%d, %d, %d>(gt::GemmP)", k.LA, k.LB, c.mt);
+    else
+        snprintf(buf, sizeof(buf), "void gt::gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %d>(gt::GemmP)", k.LA, k.LB, c.mt, c.nt, c.wm,
+                 c.wn, k.BK, k.family == F32_HEAD ? (k.n_out == 1 ? 1 : 4) : 0);
+    return buf;
+}
+
+// C_z = alpha * sum over the `split` slabs [split][batch0 * batch1][M][N] in ws (what a raw split-K launch of any engine left)
+int splitk_reduce_launch(const float* slabs, int split, int M, int N, int batch0, int batch1, float alpha, float* C, int64_t ldc,
+                         int64_t c_bs0, int64_t c_bs1, hipStream_t st) {
+    const int64_t mn = (int64_t)M * N, total = (int64_t)batch0 * batch1 * mn;
+    if (((N | ldc | c_bs0 | c_bs1) & 3) == 0 && !misaligned16(C, slabs)) {
+        const int64_t total4 = total / 4;
+        const int blocks4 = (int)((total4 + 31) / 32);
+        hipLaunchKernelGGL(splitk_reduce4_kernel, dim3(blocks4), dim3(256), 0, st, slabs, split, total, M, N / 4, batch1, alpha, C,
+                           ldc, c_bs0, c_bs1, total4);
+    } else {
         const int blocks = (int)std::min<int64_t>((total + 255) / 256, 2048);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st,
-                           reinterpret_cast<const float*>(ws), pl.split, batch * mn, d->M, d->N,
-                           d->batch1, d->alpha, d->C, d->ldc, d->c_bs0, d->c_bs1, total);
-        GT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, slabs, split, total, M, N, batch1, alpha, C, ldc,
+                           c_bs0, c_bs1, total);
     }
+    GT_LAUNCH_CHECK();
     return 0;
 }
 
-// Splits d into the 128-aligned column range `a` and the remainder `b` when that pays (see gt_gemm); false otherwise.
-static bool width_split(const gt_gemm_desc* d, gt_gemm_desc* a, gt_gemm_desc* b) {
-    const int rem = d->N % 128;
-    Plan pl;
-    if (!(d->N > 128 && rem != 0 && rem <= 64 && d->ep_mode == GT_EP_NORMAL && d->cv_c == 0 && make_plan(d, &pl) == 0 &&
-          pl.bn == 128))
-        return false;
-    // only when the aligned part alone fills the chip: two half-empty launches would serialise instead.  One launch
-    // per tile (split == 1): >= 512 tiles (measured);  K-split products (token-contracted, no epilogue): the K
-    // slices of the aligned part fill it
-    const int64_t main_tiles = (int64_t)pl.tiles_m * (d->N / 128) * d->batch0 * d->batch1;
-    if (pl.split == 1 ? main_tiles < 512 : (main_tiles * pl.split < 256 || d->K2 > 0)) return false;
-    const int n_main = d->N - rem;
-    *a = *d;
-    *b = *d;
-    a->N = n_main;
-    b->N = rem;
-    b->B = d->B + (d->layout_b == 0 ? (int64_t)n_main * d->ldb : (int64_t)n_main);
-    b->C = d->C + n_main;
-    if (d->K2 > 0) b->B2 = d->B2 + (d->layout_b == 0 ? (int64_t)n_main * d->ldb2 : (int64_t)n_main);
-    if (d->bias) b->bias = d->bias + n_main;
-    if (d->rp) b->rp_b = d->rp_b + (int64_t)n_main * d->rp_ldb;
-    if (d->add) b->add = d->add + n_main;
-    if (d->pre) b->pre = d->pre + n_main;
-    if (d->aux) b->aux = d->aux + n_main;
-    if (d->res) b->res = d->res + n_main;
-    if (d->c_masked) b->c_masked = d->c_masked + n_main;
-    if (pl.split == 1) a->split_k = b->split_k = 1;      // else: each part plans its own K slices (split_k as given)
-    b->a_colsum = nullptr;                               // the row sums of A ride on the first launch only
-    return true;
-}
-
-// Widths just above a multiple of 128 (the merged-head width h*(d_k+p) = 144 of the Darcy model) would
-// waste most of a second 128-wide tile column: run the aligned part and the remainder as two launches,
-// the remainder on a narrow-tile configuration.
-// > 0: gt_gemm(d) is ONE launch of the packed-B kernels and this is the size of its packed weight (the buffer a caller that
-// packs ahead -- gt_gemm_pack_b_many -- hands over in d->b_packed); 0: some other path, b_packed must stay NULL
-static int64_t packed_bytes_one(const gt_gemm_desc* d) {
-    Plan pl;
-    if (!getenv("GT_GEMM_NO_TSMM") && tsmm_eligible(d)) return 0;
-    if (make_plan(d, &pl) || !pl.x3 || !x3_packed_ok(d, pl.x3, pl.split)) return 0;
-    return x3_packed_bytes(d);
-}
-
-// Round 6: a width-split product (N = 192 = 128 + 64, ex3's d_model) is TWO packed-B launches when both column ranges take
-// the packed kernels; its packed weight is the two packs back to back (the aligned range first).
-extern "C" int64_t gt_gemm_packed_b_bytes(const gt_gemm_desc* d) {
-    if (!d) return 0;
-    gt_gemm_desc a, b, hs;
-    d = hn_slots(d, &hs);
-    if (width_split(d, &a, &b)) {
-        a.b_packed = b.b_packed = nullptr;
-        const int64_t pa = packed_bytes_one(&a), pb = packed_bytes_one(&b);
-        return (pa > 0 && pb > 0) ? pa + pb : 0;
-    }
-    return packed_bytes_one(d);
-}
-
-extern "C" int gt_gemm_pack_b_many(const gt_gemm_desc* descs, void* const* outs, int32_t n, void* stream) {
-    if (!descs || !outs || n < 0 || n > 64) return GT_EINVAL;
-    gt_gemm_desc parts[128];
-    void* pouts[128];
-    int m = 0;
-    for (int i = 0; i < n; ++i) {
-        if (gt_gemm_packed_b_bytes(&descs[i]) <= 0) return GT_ENOTSUP;
-        gt_gemm_desc a, b, hs;
-        const gt_gemm_desc* di = hn_slots(&descs[i], &hs);
-        if (di != &descs[i]) {
-            parts[m] = *di; pouts[m++] = outs[i];
-        } else if (width_split(&descs[i], &a, &b)) {
-            a.b_packed = b.b_packed = nullptr;
-            parts[m] = a; pouts[m++] = outs[i];
-            parts[m] = b; pouts[m++] = reinterpret_cast<char*>(outs[i]) + packed_bytes_one(&a);
-        } else {
-            parts[m] = descs[i]; pouts[m++] = outs[i];
-        }
-    }
-    for (int i0 = 0; i0 < m; i0 += 64) {
-        int rc = x3_pack_b_many(parts + i0, pouts + i0, std::min(64, m - i0), (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-extern "C" int gt_gemm(const gt_gemm_desc* d, void* ws, int64_t ws_bytes, void* stream) {
-    if (!d) return GT_EINVAL;
-    gt_gemm_desc a, b, hs;
-    d = hn_slots(d, &hs);
-    if (width_split(d, &a, &b)) {
-        // a weight packed ahead is the two column ranges' packs back to back (gt_gemm_packed_b_bytes): each range gets ITS
-        // pack -- never the full-width pointer with the wrong tile geometry
-        if (d->b_packed) {
-            a.b_packed = b.b_packed = nullptr;
-            const int64_t pa = packed_bytes_one(&a);
-            if (pa <= 0 || packed_bytes_one(&b) <= 0) return GT_EINVAL;
-            a.b_packed = d->b_packed;
-            b.b_packed = reinterpret_cast<const char*>(d->b_packed) + pa;
-        }
-        int rc = gemm_one(&a, d->N, 0, ws, ws_bytes, stream);
-        if (rc) return rc;
-        return gemm_one(&b, d->N, a.N, ws, ws_bytes, stream);      // same stream: the scratch is free again
-    }
-    return gemm_one(d, d->N, 0, ws, ws_bytes, stream);
-}
+}  // namespace gt

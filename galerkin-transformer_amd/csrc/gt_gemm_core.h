@@ -1,5 +1,6 @@
-// Shared pieces of the GEMM engine (gt_gemm.hip: fp32-MFMA kernels; gt_gemm_x3.hip: split-operand bf16-MFMA
-// kernel): the launch-parameter block, the operand loaders and the fused epilogue.  gfx950 only.
+// Shared pieces of the GEMM engine (gt_gemm_desc.hip: descriptor layer -- plan, route, validation, the C entry points;
+// gt_gemm.hip: fp32-MFMA kernels and their launchers; gt_gemm_x3*.hip: split-operand kernels): the launch-parameter block, the
+// operand loaders, the fused epilogue and what the descriptor layer asks of each kernel unit.  gfx950 only.
 #pragma once
 #include "gt_common.h"
 
@@ -31,7 +32,7 @@ struct GemmP {
     const float* hn_gamma; const float* hn_beta; const float* hn_pos; float* hn_out; float* hn_stats;
     int hn_h, hn_dk, hn_p, hn_DP, hn_mask, hn_skip_raw, hn_plain; float hn_eps;
     float* c2; int64_t ldc2; DropDev drop2;   // gt_gemm_desc.c_masked: the result once more under a second dropout mask
-    int hn_dkr;              // real head width: == hn_dk, or 48 inside hn_dk = 64-column head SLOTS (gt_gemm.hip: hn_slots)
+    int hn_dkr;              // real head width: == hn_dk, or 48 inside hn_dk = 64-column head SLOTS (gt_gemm_desc.hip: hn_slots)
     int cv_H, cv_W, cv_C, cv_wgrad;  // implicit 3x3 convolution (gt_hip.h: cv_*), cv_C = 0: plain GEMM
     const void* Bp; int bp_NT, bp_KS, bp_f16; // packed-B kernel (gt_gemm_x3.hip): bf16 (fp16: bp_f16) planes of B in fragment order
     int wg_f16;                              // gemm_x3w_kernel: the GT_PREC_F16X2 token-contracted weight gradient
@@ -410,6 +411,19 @@ __device__ __forceinline__ void head_epilogue(const GemmP& p, const f32x4 (&acc)
     }
 }
 
+
+// fp32-MFMA kernels (gt_gemm.hip).  The instance f32_launch starts and f32_kernel_name prints: the family and the template
+// arguments it takes from these (cfg indexes kF32Cfgs; n_out: the head instances exist for 1 and for up to 4 outputs).
+struct F32Cfg { int mt, nt, wm, wn; };              // block = wm x wn waves, each (16 mt) x (16 nt) of the output tile
+constexpr int kNumF32Cfg = 5;
+constexpr F32Cfg kF32Cfgs[kNumF32Cfg] = {{4, 4, 2, 2}, {2, 4, 2, 2}, {2, 2, 2, 2}, {2, 2, 4, 1}, {2, 1, 4, 1}};
+enum F32Family { F32_TILE, F32_HEAD, F32_STREAM };  // gemm_kernel<.., 0> / gemm_kernel<0, 0, .., 16, 1 | 4> / gemm_stream_kernel
+struct F32Pick { F32Family family; int LA, LB, cfg, BK, n_out; };
+int f32_launch(const GemmP& p, const F32Pick& k, dim3 grid, hipStream_t st);
+const char* f32_kernel_name(const F32Pick& k);
+// C_z = alpha * sum of the raw K-slice slabs [split][batch0 * batch1][M][N] a split-K launch of either engine left
+int splitk_reduce_launch(const float* slabs, int split, int M, int N, int batch0, int batch1, float alpha, float* C, int64_t ldc,
+                         int64_t c_bs0, int64_t c_bs1, hipStream_t st);
 
 // split-operand kernels: host dispatch in gt_gemm_x3.hip, kernel families in gt_gemm_x3.hip / gt_gemm_x3p.hip / gt_gemm_x3w.hip
 // The instance x3_launch starts and x3_kernel_name prints: the family and the template arguments it takes from these.

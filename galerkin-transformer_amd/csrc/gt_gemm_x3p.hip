@@ -15,7 +15,7 @@ namespace gt {
 // requested at the top of iteration kt into a second register set; the counted waits (vector-memory loads retire in
 // order) are written out next to the loop.
 // Row of the weight behind tile row n (pad48: the tile rows are 64-column head slots holding 48-wide heads, the 16 rows behind
-// a head are zero -- gt_gemm.hip: hn_slots; N counts slot rows then), -1: a zero row.
+// a head are zero -- gt_gemm_desc.hip: hn_slots; N counts slot rows then), -1: a zero row.
 __device__ __forceinline__ int x3_pack_row(int n, int N, int pad48) {
     if (n >= N) return -1;
     if (!pad48) return n;
@@ -376,7 +376,7 @@ static inline int x3p_ks(int K) { return (K + X3_BK - 1) / X3_BK; }
 
 int64_t x3_packed_bytes(const gt_gemm_desc* d) { return (int64_t)3 * x3p_nt(d->N) * x3p_ks(d->K) * 1024; }
 
-// the descriptor (already in head slots, gt_gemm.hip: hn_slots) describes 48-wide heads in 64-column slots
+// the descriptor (already in head slots, gt_gemm_desc.hip: hn_slots) describes 48-wide heads in 64-column slots
 static inline int x3_pad48(const gt_gemm_desc* d) {
     return d->ep_mode == GT_EP_HEADNORM && d->hn_dk == 48 && d->N == 3 * d->hn_h * 64;
 }

@@ -1304,7 +1304,7 @@ def test_plain_head_tiles_ktv_and_dkv_ln(H, gpu_device, B, n, h, dk, p):
 def test_qkv_headnorm_head_slots_dk48(H, gpu_device, T, mask, prec):
     """Round 6: GT_EP_HEADNORM for 48-wide heads (ex3: d_model 192, 4 heads; reference layers.py:838-874 with d_k = 48) on the
     packed-B kernels -- every head in a 64-column slot of the tile, the 16 columns behind it zero rows of the packed weight
-    (gt_gemm.hip: hn_slots) -- against gt_gemm + gt_headnorm_fwd: head tiles, statistics, the raw projection where it is
+    (gt_gemm_desc.hip: hn_slots) -- against gt_gemm + gt_headnorm_fwd: head tiles, statistics, the raw projection where it is
     written (skip_raw), plain tiles without any raw projection, and the weight packed ahead (gt_gemm_pack_b_many)."""
     import ctypes as C
     dev = gpu_device
@@ -2235,3 +2235,99 @@ def test_gemm_f16x2_weight_gradient_kernel(H, gpu_device, M, N, K):
     C2, cs2 = torch.empty(M, N, device=dev), torch.empty(M, device=dev)
     H.gemm(Ad, Bd, C2, M, N, K, layout_a=1, layout_b=1, lda=M, ldb=N, ldc=N, split_k=0, a_colsum=cs2, precision="f16x2")
     assert torch.equal(C, C2) and torch.equal(cs, cs2)
+
+
+# ---- gt_gemm's refusals: one descriptor per return site of the descriptor layer, each with ONE defect (then six with two, which
+# pin the order of the checks).  Every pointer that is not itself the defect is a real tensor big enough for the shapes
+# (M, N <= 256, K <= 512), so a descriptor accepted by mistake would run a small valid product, not a wild access.
+# Base: fp32, la = lb = 0, M = N = 128, K = 64, split_k = 1.
+_EINVAL, _EWS, _ENOTSUP = -1, -3, -4
+_HN = dict(ep_mode=3, N=96, hn_h=1, hn_dk=32, hn_out=True, hn_gamma=True, hn_beta=True, hn_stats=True, hn_norm_mask=3, precision=1)
+_HEAD = dict(n_out=1, w2=True, ldw2=128, out2=True, g2=True, dw2=True)
+_CONV = dict(cv_h=8, cv_w=16, cv_c=16, K=144, lda=16, ldb=144, precision=1)                       # 128 pixels, 16 channels
+_CONVW = dict(cv_h=8, cv_w=16, cv_c=16, cv_wgrad=1, layout_a=1, layout_b=1, M=64, N=16, K=128, lda=64, ldb=16, ldc=16, batch0=9,
+              c_bs0=64 * 16, split_k=0, precision=1)
+_K2 = dict(K2=16, A2=True, B2=True, lda2=16, ldb2=16)
+_SPLIT4 = dict(K=512, lda=512, ldb=512, split_k=4)
+_GEMM_REFUSALS = [
+    ("null-c", dict(C=None), _EINVAL),
+    ("layout-2", dict(layout_a=2), _EINVAL),
+    ("ep-mode-7", dict(ep_mode=7), _EINVAL),
+    ("headnorm-la1", dict(_HN, layout_a=1), _ENOTSUP),
+    ("headnorm-wrong-n", dict(_HN, N=128), _EINVAL),
+    ("headnorm-mask-no-stats", dict(_HN, hn_stats=None), _EINVAL),
+    ("headnorm-act", dict(_HN, act=1), _ENOTSUP),
+    ("headnorm-f32", dict(_HN, precision=0), _ENOTSUP),
+    ("rowdot-n160", dict(_HEAD, ep_mode=1, N=160, ldc=160, ldw2=160), _ENOTSUP),
+    ("rowdot-no-out2", dict(_HEAD, ep_mode=1, out2=None), _EINVAL),
+    ("rowdot-lb1", dict(_HEAD, ep_mode=1, layout_b=1, ldb=128), _ENOTSUP),
+    ("mlp-bwd-no-ws", dict(_HEAD, ep_mode=2, ws=None), _EWS),
+    ("conv-k", dict(_CONV, K=128), _EINVAL),
+    ("conv-c8", dict(_CONV, cv_c=8, K=72, lda=8, ldb=72), _ENOTSUP),
+    ("conv-f32", dict(_CONV, precision=0), _ENOTSUP),
+    ("convw-batch", dict(_CONVW, batch0=1), _EINVAL),
+    ("convw-w8", dict(_CONVW, cv_h=16, cv_w=8), _ENOTSUP),
+    ("rp-9", dict(rp=9, rp_a=True, rp_b=True, rp_lda=9, rp_ldb=9), _EINVAL),
+    ("rp-no-a", dict(rp=2, rp_b=True, rp_lda=2, rp_ldb=2), _EINVAL),
+    ("drop-no-seed", dict(drop=(0.1, False)), _EINVAL),
+    ("drop-p1", dict(drop=(1.0, True)), _EINVAL),
+    ("split4-bias", dict(_SPLIT4, bias=True), _ENOTSUP),
+    ("split4-small-ws", dict(_SPLIT4, ws=1024), _EWS),
+    ("k2-no-a2", dict(_K2, A2=None), _ENOTSUP),
+    ("colsum-la0", dict(a_colsum=True), _ENOTSUP),
+    ("c-masked-batch2", dict(c_masked=True, ldc_masked=128, batch0=2, a_bs0=128 * 64, c_bs0=128 * 128), _ENOTSUP),
+    ("c-mask-p1", dict(c_masked=True, ldc_masked=128, c_mask=(1.0, True)), _EINVAL),
+    ("aux-op-no-aux", dict(aux_op=1), _EINVAL),
+    ("b-packed-not-packed", dict(b_packed=True), _EINVAL),
+    ("precision-7", dict(precision=7), _EINVAL),
+    ("act-gelu", dict(act=3), _EINVAL),
+    ("batch-90000", dict(M=16, N=16, K=16, lda=16, ldb=16, ldc=16, batch0=300, batch1=300), _EINVAL),
+    # two defects: the first check in the order of the descriptor layer answers
+    ("rp-9+split4-bias", dict(_SPLIT4, bias=True, rp=9, rp_a=True, rp_b=True, rp_lda=9, rp_ldb=9), _EINVAL),     # not ENOTSUP
+    ("precision-7+rp-9", dict(precision=7, rp=9, rp_a=True, rp_b=True, rp_lda=9, rp_ldb=9), _EINVAL),
+    ("k2-no-a2+split4-small-ws", dict(_SPLIT4, **dict(_K2, A2=None), ws=1024), _ENOTSUP),                        # the plan, not EWS
+    ("null-c+colsum-la0", dict(C=None, a_colsum=True), _EINVAL),                                                 # not ENOTSUP
+    ("mlp-bwd-no-ws+lb1", dict(_HEAD, ep_mode=2, layout_b=1, ldb=128, ws=None), _EWS),                           # not ENOTSUP
+    ("split4-small-ws+b-packed", dict(_SPLIT4, ws=1024, b_packed=True), _EWS),                                   # not EINVAL
+]
+_GEMM_PTRS = ("A", "B", "C", "A2", "B2", "bias", "res", "add", "pre", "aux", "rp_a", "rp_b", "a_colsum", "c_masked", "b_packed", "w2",
+              "b2", "out2", "g2", "dw2", "hn_gamma", "hn_beta", "hn_pos", "hn_out", "hn_stats")
+
+
+def gemm_refusal_rc(H, dev, fields, pool):
+    """gt_gemm's return code for the base product with `fields` laid over it.  pool: name -> tensor, filled on demand."""
+    import ctypes as C
+
+    def buf(name, dtype=torch.float32):
+        if name not in pool:
+            pool[name] = torch.zeros(256 * 512, dtype=dtype, device=dev)        # the largest operand any case describes
+        return pool[name]
+    L = H.lib()
+    d = H.GtGemmDesc()
+    L.gt_gemm_desc_init(C.byref(d))
+    f = dict(M=128, N=128, K=64, lda=64, ldb=64, ldc=128, A=True, B=True, C=True, ws=1 << 20)
+    f.update(fields)
+    ws = f.pop("ws")
+    for k, v in f.items():
+        if k in ("drop", "a_drop", "c_mask"):
+            g = getattr(d, k)
+            g.p, g.salt, g.seed = v[0], 5, buf("seed", torch.int64).data_ptr() if v[1] else None
+        elif k in _GEMM_PTRS:
+            setattr(d, k, buf(k).data_ptr() if v else None)
+        else:
+            setattr(d, k, v)
+    wsp = buf("ws").data_ptr() if ws else None                        # 512 KiB of real scratch; `ws` = the size we admit to
+    return L.gt_gemm(C.byref(d), wsp, min(ws or 0, 4 * 256 * 512), H.stream_ptr())
+
+
+@pytest.fixture(scope="module")
+def refusal_pool():
+    return {}
+
+
+@pytest.mark.parametrize("name,fields,want", _GEMM_REFUSALS, ids=[c[0] for c in _GEMM_REFUSALS])
+def test_gemm_refusal_codes(H, gpu_device, refusal_pool, name, fields, want):
+    """The code gt_gemm refuses a descriptor with is behaviour (the Python side falls back on GT_ENOTSUP only), and with two
+    defects the order of the checks decides it."""
+    assert gemm_refusal_rc(H, gpu_device, fields, refusal_pool) == want
+    torch.cuda.synchronize()

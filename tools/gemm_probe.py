@@ -15,7 +15,6 @@ sk = int(os.environ.get("SPLITK", 0 if la == 1 else 1))
 f = lambda: H.gemm(A, B, C, M, N, K, layout_a=la, layout_b=lb, lda=A.shape[2], ldb=B.shape[2], ldc=N, split_k=sk,
                    batch=(nb, 1), a_bs=(A.shape[1] * A.shape[2], 0), b_bs=(B.shape[1] * B.shape[2], 0), c_bs=(M * N, 0))
 f(); torch.cuda.synchronize()
-os.environ.pop("GT_GEMM_DEBUG", None)
 for _ in range(3): f()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record()

@@ -219,6 +219,12 @@ _PROTOS = {
     "gt_h1loss2d_final": (C.c_int, [C.c_int32] * 3 + [C.c_float] * 4 + [C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
     "gt_h1loss2d_bwd": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + [C.c_int32] * 3 + [C.c_float] * 3 +
                         [C.c_void_p, C.c_void_p]),
+    "gt_h1loss1d_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "gt_h1loss1d_fwd": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_float, C.c_int32,
+                                                                                             C.c_void_p, C.c_int64, C.c_void_p]),
+    "gt_h1loss1d_final": (C.c_int, [C.c_int32] * 3 + [C.c_float] * 3 + [C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
+    "gt_h1loss1d_bwd": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_float] * 3 +
+                        [C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
@@ -1600,4 +1606,52 @@ def h1loss2d_bwd(P: torch.Tensor, T: torch.Tensor, G: Optional[torch.Tensor], K:
     px = float(N) * n * n
     _launch("gt_h1loss2d_bwd", P, ldp, T, G, K, L2, H1, gl, gr, N, n, int(dilation), float(h), float(beta), float(gamma), dP,
             nbytes=4.0 * px * (3 + (0 if G is None or gr is None else 2 + (0 if K is None else 1))), shape=(N, n, ldp))
+    return dP
+
+
+# ----------------------------------------------------------------------------------- 1-D training objective
+def h1loss1d_pitch(P: torch.Tensor) -> Optional[int]:
+    """Element pitch (in floats) of an [N, L] tensor whose elements are evenly spaced in memory -- a contiguous tensor (1) or
+    channel 0 of a contiguous [N, L, c] one (c); None for any other strides."""
+    N, L = P.shape
+    ld = P.stride(1)
+    ok = ld >= 1 and (P.stride(0) == L * ld or N == 1)
+    return ld if ok else None
+
+
+def h1loss1d_fwd(P: torch.Tensor, T: torch.Tensor, G: Optional[torch.Tensor], dilation: int, h: float, beta: float,
+                 gamma_h: float, want_reg: bool):
+    """Per-sample terms of WeightedL2Loss (gt_h1loss1d_fwd + gt_h1loss1d_final).  P [N, L] with an even element pitch
+    (h1loss1d_pitch), T [N, L], G [N, L] or None; T, G contiguous.  gamma_h is the regulariser's weight times h, as the
+    class stores it.  Returns (loss [N], reg [N] or None, L2 [N], H1 [N])."""
+    need_f32_cuda(P, T, G)
+    N, L = P.shape
+    ldp = h1loss1d_pitch(P)
+    if ldp is None or not (T.is_contiguous() and (G is None or G.is_contiguous())):
+        raise ValueError("h1loss1d_fwd: P needs evenly pitched elements, T / G must be contiguous")
+    if T.shape != P.shape or (G is not None and G.shape != P.shape):
+        raise ValueError("h1loss1d_fwd: T [N, L], G [N, L] expected")
+    out = torch.empty(4 if want_reg else 3, N, dtype=torch.float32, device=P.device)
+    loss, L2, H1, reg = out[0], out[1], out[2], (out[3] if want_reg else None)
+    wsb = lib().gt_h1loss1d_ws_bytes(N, L)
+    ws = workspace(P.device, max(16, wsb))
+    _launch("gt_h1loss1d_fwd", P, ldp, T, G, N, L, int(dilation), float(h), int(bool(want_reg)), ws=ws,
+            nbytes=4.0 * N * L * (2 + (0 if G is None else 1)), shape=(N, L, ldp))
+    _launch("gt_h1loss1d_final", N, L, int(dilation), float(h), float(beta), float(gamma_h), int(G is not None),
+            loss, reg, L2, H1, ws=ws, nbytes=float(wsb), shape=(N, L))
+    return loss, reg, L2, H1
+
+
+def h1loss1d_bwd(P: torch.Tensor, T: torch.Tensor, G: Optional[torch.Tensor], L2: torch.Tensor, H1: torch.Tensor,
+                 gl: Optional[torch.Tensor], gr: Optional[torch.Tensor], dilation: int, h: float, beta: float,
+                 gamma_h: float) -> torch.Tensor:
+    """dP [N, L] (dense) of h1loss1d_fwd from the upstream gradients gl, gr [N] of loss and reg (None = no gradient)."""
+    need_f32_cuda(P, T, G, L2, H1, gl, gr)
+    N, L = P.shape
+    ldp = h1loss1d_pitch(P)
+    if ldp is None or not all(t is None or t.is_contiguous() for t in (T, G, L2, H1, gl, gr)):
+        raise ValueError("h1loss1d_bwd: P needs evenly pitched elements, every other tensor must be contiguous")
+    dP = torch.empty(N, L, dtype=torch.float32, device=P.device)
+    _launch("gt_h1loss1d_bwd", P, ldp, T, G, L2, H1, gl, gr, N, L, int(dilation), float(h), float(beta), float(gamma_h), dP,
+            nbytes=4.0 * N * L * (3 + (0 if G is None or gr is None else 1)), shape=(N, L, ldp))
     return dP

@@ -1,7 +1,8 @@
 """Data containers, normaliser and losses with the reference's names (reference: libs/ft.py).
 
 These are host-side / few-kernels-per-step pieces outside the HIP hot path:
-they are plain PyTorch, except WeightedL2Loss2d.terms(), whose device float32 calls run on ops.weighted_l2_terms_2d.  The ``.mat`` datasets of the reference are not redistributable; the
+they are plain PyTorch, except WeightedL2Loss.terms() and WeightedL2Loss2d.terms(), whose device float32 calls run on
+ops.weighted_l2_terms_1d / _2d.  The ``.mat`` datasets of the reference are not redistributable; the
 dataset classes load them when ``DATA_PATH`` provides the files and otherwise synthesise tensors
 of the same shapes (``synthetic=True``), which is what the benchmarks use.
 """
@@ -325,7 +326,7 @@ class WeightedL2Loss(_WeightedLoss):
         d = self.dilation
         return (x[:, d:] - x[:, :-d]) / d / h
 
-    def _reduce(self, v):
+    def reduce(self, v):
         return v.sqrt().mean() if self.return_norm else v.mean()
 
     def _orthogonalizer(self, preds_latent):
@@ -340,36 +341,71 @@ class WeightedL2Loss(_WeightedLoss):
             with torch.no_grad():
                 diag = torch.diag_embed(y.pow(2).sum(dim=-1 if local else -2))
             terms.append(self.delta * (gram - diag).pow(2).mean(dim=(-1, -2)))
-        return self._reduce(torch.stack(terms, dim=-1))
+        return self.reduce(torch.stack(terms, dim=-1))
 
-    def forward(self, preds, targets, preds_prime=None, targets_prime=None, preds_latent: list = [],
-                K=None):
-        h = self.h
+    def _hip_terms_ok(self, preds, targets, preds_prime=None, targets_prime=None, K=None):
+        """Whether terms() takes the HIP operator (ops.weighted_l2_terms_1d) for this call.  Pure: reads is_cuda, dtype,
+        shape, ndim and requires_grad of its arguments and nothing else."""
+        if not (preds.is_cuda and preds.dtype == torch.float32 and preds.ndim == 2 and preds.shape[1] > self.dilation):
+            return False
+        if not (preds_prime is None or self.alpha == 0):
+            return False
+        for t in (targets, targets_prime):
+            if t is not None and (tuple(t.shape) != tuple(preds.shape) or t.requires_grad or not t.is_cuda
+                                  or t.dtype != torch.float32):
+                return False
+        return True
+
+    def _noisy(self, targets):
         if self.noise > 0:
             assert 0 <= self.noise <= 0.2
             with torch.no_grad():
                 targets = targets * (1.0 + self.noise * torch.rand_like(targets))
+        return targets
+
+    def terms(self, preds, targets, preds_prime=None, targets_prime=None, K=None):
+        """Per-sample relative errors without any host read-back (what a captured training step uses):
+        (loss [N], regulariser [N] or None, dict(L2=target norm, H1=target derivative norm or 1)).  forward() reduces
+        them and adds the metric and the orthogonaliser.  Device float32 calls without the alpha term run on the HIP
+        operator, everything else on _terms_torch()."""
+        hip = self._hip_terms_ok(preds, targets, preds_prime, targets_prime, K)
+        targets = self._noisy(targets)
+        if not hip:
+            return self._terms_torch(preds, targets, preds_prime, targets_prime, K)
+        from .ops import weighted_l2_terms_1d
+        loss, reg, L2, H1 = weighted_l2_terms_1d(preds, targets, targets_prime, dilation=self.dilation, h=self.h,
+                                                 beta=self.beta, gamma_h=self.gamma, regularizer=self.regularizer)
+        return loss, reg, dict(L2=L2, H1=H1 if targets_prime is not None else 1)
+
+    def _terms_torch(self, preds, targets, preds_prime=None, targets_prime=None, K=None):
+        """terms() in plain torch (`noise` already applied): the route of CPU tensors, other dtypes, the alpha term and
+        differentiable targets."""
+        h = self.h
         target_norm = h * targets.pow(2).sum(dim=1)
         targets_prime_norm = h * targets_prime.pow(2).sum(dim=1) if targets_prime is not None else 1
         loss = self.beta * (h * (preds - targets).pow(2)).sum(dim=1) / target_norm
         if preds_prime is not None and self.alpha > 0:
             loss = loss + self.alpha * (h * (preds_prime - K * targets_prime).pow(2)).sum(dim=1) \
                 / targets_prime_norm
+        reg = None
+        if self.regularizer and self.gamma > 0 and targets_prime is not None:
+            s = self.dilation // 2
+            reg = self.gamma * h * (targets_prime[:, s:-s] - self.central_diff(preds)).pow(2).sum(dim=1) \
+                / targets_prime_norm
+        return loss, reg, dict(L2=target_norm, H1=targets_prime_norm)
+
+    def forward(self, preds, targets, preds_prime=None, targets_prime=None, preds_latent: list = [],
+                K=None):
+        loss, reg, _ = self.terms(preds, targets, preds_prime, targets_prime, K)
         if self.metric_reduction == 'L2':
             metric = loss.mean().sqrt().item()
         elif self.metric_reduction == 'L1':
             metric = loss.sqrt().mean().item()
         elif self.metric_reduction == 'Linf':
             metric = loss.sqrt().max().item()
-        loss = self._reduce(loss)
+        loss = self.reduce(loss)
         zero = lambda: torch.tensor([0.0], requires_grad=True, device=preds.device)
-        if self.regularizer and self.gamma > 0 and targets_prime is not None:
-            s = self.dilation // 2
-            reg = self.gamma * h * (targets_prime[:, s:-s] - self.central_diff(preds)).pow(2).sum(dim=1) \
-                / targets_prime_norm
-            reg = self._reduce(reg)
-        else:
-            reg = zero()
+        reg = self.reduce(reg) if reg is not None else zero()
         ortho = self._orthogonalizer(preds_latent) if (self.orthogonal_reg > 0 and preds_latent) else zero()
         return loss, reg, ortho, metric
 

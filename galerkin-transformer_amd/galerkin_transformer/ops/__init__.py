@@ -14,7 +14,7 @@ One module per operator family; this file only re-exports (every name is the obj
 ``conv``         conv0 + resize, the wide channels-last 3x3 convolution, the chain of three narrow ones; their filter
                  layouts, weight-gradient route, library fallback, eligibility functions and switches
 ``dense``        ``packed_params``, Linear, the regression head, FeedForward, FeedForward with BatchNorm1d
-``loss``         the 2-D weighted-L2 / H1 objective per sample, ``H1Loss2dFn``
+``loss``         the weighted-L2 / H1 objectives per sample: ``H1Loss2dFn`` (2-D), ``H1Loss1dFn`` (1-D)
 ``attention``    the attention-dropout mode and mask queue, ``SimpleAttentionFn`` with its projection stage and cores,
                  ``CrossAttentionFn`` on the same cores
 """
@@ -32,6 +32,6 @@ from .dense import (FeedForwardBNFn, FeedForwardFn, LinearFn, MlpHeadFn, _check_
                     feed_forward, feed_forward_bn, linear, mlp_head, packed_params)
 from .elementwise import (DropActFn, DropoutFn, LayerNormFn, _c, _next_salt, drop_act, dropout,  # noqa: F401
                           layer_norm)
-from .loss import H1Loss2dFn, weighted_l2_terms_2d  # noqa: F401
+from .loss import H1Loss1dFn, H1Loss2dFn, weighted_l2_terms_1d, weighted_l2_terms_2d  # noqa: F401
 from .resize import (ResizeFn, ResizeSegFn, UpsampleFcFn, bilinear_resize, bilinear_resize_seg, out_size,  # noqa: F401
                      upsample_fc)

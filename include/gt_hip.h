@@ -822,6 +822,37 @@ int gt_h1loss2d_bwd(const float* P, int64_t ldp, const float* T, const float* G,
                     const float* H1, const float* gl, const float* gr, int32_t N, int32_t n, int32_t dilation, float h,
                     float beta, float gamma, float* dP, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The 1-D training objective, per sample (ft.py:898-980, WeightedL2Loss.forward without its alpha term, its noise and its
+ * orthogonaliser; ABI v21, additive).  P, T [N][L] prediction and target, G [N][L] target derivative (optional).  Even
+ * dilation d < L, s = d / 2:
+ *     A = sum T^2     E = sum (P - T)^2     Gs = sum G^2
+ *     D P[c] = (P[c+s] - P[c-s]) / (d h)  and  R = sum (G[c] - D P[c])^2   over s <= c < L - s
+ *     L2 = h A      H1 = h Gs  (1 without G)                              -- no eps, as the reference
+ *     loss = beta h E / L2      reg = gamma_h h R / H1                    -- gamma_h: the class stores gamma h
+ *   gt_h1loss1d_fwd    one streaming pass: per-block partial sums of (A, E, Gs, R) into ws.  want_reg == 0: R is not formed;
+ *                      G == NULL: Gs neither (want_reg != 0 then: GT_EINVAL)
+ *   gt_h1loss1d_final  merges the partials of each sample in block order, in double, and writes loss, L2, H1 [N] and, unless
+ *                      NULL, reg [N].  has_g: whether the forward had G.  Same N, L and ws as the forward, same stream
+ *   gt_h1loss1d_bwd    dP [N][L], dense, from the upstream gradients gl, gr [N] of loss and reg (either may be NULL = 0) and
+ *                      the L2, H1 the final pass wrote.  With r[c] = D P[c] - G[c] on s <= c < L - s and 0 elsewhere:
+ *                        dP[i] = gl beta h 2 / L2 (P - T)[i] + gr gamma_h h 2 / H1 / (d h) (r[i-s] - r[i+s])
+ *                      a gather: every element recomputes the at most two residuals it feeds
+ * P is read with the element pitch ldp >= 1 in floats (the callers pass channel 0 of an [N][L][c] tensor); T, G, dP are
+ * dense.  fp32, the merge in double; no atomics: bit-identical from run to run.  The caller's stream, no allocation, no host
+ * read-back.  16-byte accesses where a tensor is 16-byte aligned (P: and ldp == 1), scalar ones otherwise.  L <= d, odd d,
+ * h <= 0, N < 1: GT_EINVAL; a pointer off a 4-byte (ws: 16-byte) boundary: GT_EALIGN; ws < gt_h1loss1d_ws_bytes(N, L): GT_EWS;
+ * more than 2^31 - 1 blocks (N ceil((L / 4 + 2) / 512)): GT_ENOTSUP.
+ * ------------------------------------------------------------------------------------------- */
+int64_t gt_h1loss1d_ws_bytes(int32_t N, int32_t L);
+int gt_h1loss1d_fwd(const float* P, int64_t ldp, const float* T, const float* G, int32_t N, int32_t L, int32_t dilation,
+                    float h, int32_t want_reg, void* ws, int64_t ws_bytes, void* stream);
+int gt_h1loss1d_final(int32_t N, int32_t L, int32_t dilation, float h, float beta, float gamma_h, int32_t has_g, float* loss,
+                      float* reg, float* L2, float* H1, const void* ws, int64_t ws_bytes, void* stream);
+int gt_h1loss1d_bwd(const float* P, int64_t ldp, const float* T, const float* G, const float* L2, const float* H1,
+                    const float* gl, const float* gr, int32_t N, int32_t L, int32_t dilation, float h, float beta,
+                    float gamma_h, float* dP, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

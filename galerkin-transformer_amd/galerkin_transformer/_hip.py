@@ -225,6 +225,14 @@ _PROTOS = {
     "gt_h1loss1d_final": (C.c_int, [C.c_int32] * 3 + [C.c_float] * 3 + [C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
     "gt_h1loss1d_bwd": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_float] * 3 +
                         [C.c_void_p, C.c_void_p]),
+    "gt_avgpool2_act_fwd": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 7 + [C.c_void_p]),
+    "gt_avgpool2_act_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 7 + [C.c_void_p]),
+    "gt_deconv3x3s2_check": (C.c_int, [C.c_int32] * 7),
+    "gt_deconv3x3s2_gather_fwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 6 + [C.POINTER(GtDropout), C.c_int32, C.c_void_p]),
+    "gt_deconv3x3s2_gather_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.POINTER(GtDropout), C.c_int32, C.c_void_p]),
+    "gt_deconv3x3s2_dbias_ws_bytes": (C.c_int64, [C.c_int32] * 6),
+    "gt_deconv3x3s2_dbias": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.POINTER(GtDropout), C.c_int32, C.c_void_p,
+                                                                           C.c_int64, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
@@ -1173,6 +1181,66 @@ def bilinear2d_seg_bwd(g: torch.Tensor, y_saved: Optional[torch.Tensor], in_size
     _launch("gt_bilinear2d_seg_bwd", g, y_saved, dx, B, Cc, Hi, Wi, Ho, Wo, act, seg, segp, x_gate, int(bool(gate_mul)),
             nbytes=4.0 * B * Cc * (Hi * Wi + 2 * Ho * Wo), shape=(B, Cc, Hi, Ho, act))
     return dx
+
+
+# ----------------------------------------------------------------------------------- 'conv' scaler modes
+def avgpool2_act_fwd(x: torch.Tensor, in_nhwc: bool, out_nhwc: bool, act: int = ACT_NONE) -> torch.Tensor:
+    """act(avg_pool2d(x, 2)): x dense [B,C,H,W] (or [B,H,W,C] when in_nhwc) -> dense [B,C,H//2,W//2] (or channels-last)."""
+    need_f32_cuda(x)
+    B, Cc, Hi, Wi = _shape4(x, in_nhwc)
+    Ho, Wo = Hi // 2, Wi // 2
+    y = torch.empty((B, Ho, Wo, Cc) if out_nhwc else (B, Cc, Ho, Wo), dtype=torch.float32, device=x.device)
+    _launch("gt_avgpool2_act_fwd", x, y, B, Cc, Hi, Wi, int(in_nhwc), int(out_nhwc), act,
+            nbytes=4.0 * B * Cc * (Hi * Wi + Ho * Wo), shape=(B, Cc, Hi, Wi, int(in_nhwc), int(out_nhwc)))
+    return y
+
+
+def avgpool2_act_bwd(x: torch.Tensor, g: torch.Tensor, in_nhwc: bool, out_nhwc: bool, act: int = ACT_NONE) -> torch.Tensor:
+    """dx (x's shape and layout) from the forward input x and the gradient g of the forward output."""
+    need_f32_cuda(x, g)
+    B, Cc, Hi, Wi = _shape4(x, in_nhwc)
+    dx = torch.empty_like(x)
+    _launch("gt_avgpool2_act_bwd", x, g, dx, B, Cc, Hi, Wi, int(in_nhwc), int(out_nhwc), act,
+            nbytes=4.0 * B * Cc * (2 * Hi * Wi + (Hi // 2) * (Wi // 2)), shape=(B, Cc, Hi, Wi, int(in_nhwc), int(out_nhwc)))
+    return dx
+
+
+def deconv3x3s2_check(B: int, Hh: int, Ww: int, Cin: int, Cout: int, pad: int, outpad: int):
+    """Raises GtNotSupported / GtError unless gt_deconv3x3s2_* take the shape; launches nothing (not a Profile record)."""
+    check(lib().gt_deconv3x3s2_check(B, Hh, Ww, Cin, Cout, pad, outpad), "gt_deconv3x3s2_check")
+
+
+def deconv3x3s2_gather_fwd(cols: torch.Tensor, bias: Optional[torch.Tensor], B: int, Hh: int, Ww: int, Cout: int, pad: int,
+                           outpad: int, out_hw, drop: Optional[GtDropout], act: int, want_pre: bool = False):
+    """cols [B*H*W, 9*Cout] -> (y [B,Ho,Wo,Cout], pre or None); see gt_hip.h."""
+    need_f32_cuda(cols, bias)
+    Ho, Wo = out_hw
+    y = torch.empty(B, Ho, Wo, Cout, dtype=torch.float32, device=cols.device)
+    pre = torch.empty_like(y) if want_pre else None
+    _launch("gt_deconv3x3s2_gather_fwd", cols, bias, y, pre, B, Hh, Ww, Cout, pad, outpad, drop, act,
+            nbytes=4.0 * Cout * B * (9 * Hh * Ww + Ho * Wo * (2 if want_pre else 1)), shape=(B, Hh, Ww, Cout, pad, outpad))
+    return y, pre
+
+
+def deconv3x3s2_gather_bwd(g: torch.Tensor, gate: Optional[torch.Tensor], B: int, Hh: int, Ww: int, Cout: int, pad: int,
+                           outpad: int, drop: Optional[GtDropout], act: int) -> torch.Tensor:
+    """g [B,Ho,Wo,Cout] -> dcols [B*H*W, 9*Cout] = the gated gradient gathered per (pixel, tap)."""
+    need_f32_cuda(g, gate)
+    dcols = torch.empty(B * Hh * Ww, 9 * Cout, dtype=torch.float32, device=g.device)
+    _launch("gt_deconv3x3s2_gather_bwd", g, gate, dcols, B, Hh, Ww, Cout, pad, outpad, drop, act,
+            nbytes=4.0 * Cout * (9 * B * Hh * Ww + g.numel() // Cout * (2 if gate is not None else 1)),
+            shape=(B, Hh, Ww, Cout, pad, outpad))
+    return dcols
+
+
+def deconv3x3s2_dbias(g: torch.Tensor, gate: Optional[torch.Tensor], B: int, Hh: int, Ww: int, Cout: int, pad: int,
+                      outpad: int, drop: Optional[GtDropout], act: int) -> torch.Tensor:
+    need_f32_cuda(g, gate)
+    db = torch.empty(Cout, dtype=torch.float32, device=g.device)
+    ws = workspace(g.device, int(lib().gt_deconv3x3s2_dbias_ws_bytes(B, Hh, Ww, Cout, pad, outpad)))
+    _launch("gt_deconv3x3s2_dbias", g, gate, db, B, Hh, Ww, Cout, pad, outpad, drop, act, ws=ws,
+            nbytes=4.0 * g.numel() * (2 if gate is not None else 1), shape=(B, Hh, Ww, Cout, pad, outpad))
+    return db
 
 
 RS_MAXT = 6          # gt_resize.hip: output rows / columns per input cell that the resize backward holds in registers

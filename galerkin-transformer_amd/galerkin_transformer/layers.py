@@ -3,7 +3,8 @@ state_dict keys (reference: libs/layers.py), whose hot-path arithmetic runs in l
 
 Hot path (HIP):  SimpleAttention (:764), FeedForward (:954), SpectralConv1d (:1040),
 SpectralConv2d (:1109).  Not on the hot path (plain PyTorch-ROCm / MIOpen, as SURVEY.md section 8
-scopes them): the conv + bilinear-interpolation scalers (:88-150, :431-512, :624-670).
+scopes them): the conv + bilinear-interpolation scalers (:88-150, :431-512, :624-670).  The 'conv' scaler modes
+(Conv2dEncoder :284-341, DeConv2dBlock :515-559) run their pools and transposed convolutions on HIP operators.
 """
 from __future__ import annotations
 
@@ -248,6 +249,89 @@ class Interp2dEncoder(nn.Module):
         if self.add_res:
             out = out + x
         return _resize(out, self.interp_size[1], self.activation, out_nhwc=out_nhwc)
+
+
+class Conv2dEncoder(nn.Module):
+    """conv0 -> AvgPool2d(2) -> act -> conv1 -> conv2 -> conv3 -> cat -> AvgPool2d(2) -> act (layers.py:284-341): the block
+    of DownScaler(downsample_mode='conv'), about 1/4 subsampling.
+
+    As in the reference the four Conv2dResBlocks get neither ``activation_type`` nor a dropout: they keep their own defaults
+    (SiLU, Dropout(0.1)) whatever the encoder's activation is; only the two activations behind the pools follow
+    ``activation_type``.  The pools (floor: an odd trailing row / column is dropped) and those activations are one HIP pass
+    each (ops.avgpool2_act); ``pool0`` / ``pool1`` are kept for the module tree.  Only scaling_factor=2 has a kernel."""
+
+    def __init__(self, in_dim: int, out_dim: int, kernel_size: int = 3, stride: int = 1, padding: int = 1, dilation: int = 1,
+                 scaling_factor: int = 2, residual=False, activation_type="silu", debug=False):
+        super().__init__()
+        c0 = out_dim // 3
+        c1 = out_dim // 3
+        c2 = int(out_dim - c0 - c1)
+        pad1 = max(padding // 2, 1)
+        pad2 = max(padding // 4, 1)
+        activation_type = default(activation_type, "silu")
+        self.conv0 = Conv2dResBlock(in_dim, out_dim, kernel_size=kernel_size, padding=padding, residual=residual)
+        self.conv1 = Conv2dResBlock(out_dim, c0, kernel_size=kernel_size, padding=pad1, stride=stride, residual=residual)
+        self.conv2 = Conv2dResBlock(c0, c1, kernel_size=kernel_size, dilation=dilation, padding=pad2, residual=residual)
+        self.conv3 = Conv2dResBlock(c1, c2, kernel_size=kernel_size, residual=residual)
+        self.pool0 = nn.AvgPool2d(kernel_size=scaling_factor, stride=scaling_factor)
+        self.pool1 = nn.AvgPool2d(kernel_size=scaling_factor, stride=scaling_factor)
+        self.activation = _act_module(activation_type)
+        self.debug = debug
+
+    def _pool_act(self, pool, x, out_nhwc=False):
+        k, s = pool.kernel_size, pool.stride
+        if not (k in (2, (2, 2)) and s in (2, (2, 2)) and pool.padding in (0, (0, 0)) and not pool.ceil_mode):
+            raise NotImplementedError(f"Conv2dEncoder: AvgPool2d(kernel_size={k}, stride={s}) has no HIP path "
+                                      "(scaling_factor=2 only)")
+        return ops.avgpool2_act(x, _act_name(self.activation), in_nhwc=False, out_nhwc=out_nhwc)
+
+    def forward(self, x, out_nhwc=False):
+        """x (B, C, H, W).  ``out_nhwc`` returns (B, H', W', C') with the layout change fused into the last pool."""
+        H.need_f32_cuda(x)
+        x = self._pool_act(self.pool0, self.conv0(x))
+        x1 = self.conv1(x)
+        x2 = self.conv2(x1)
+        x3 = self.conv3(x2)
+        return self._pool_act(self.pool1, torch.cat([x1, x2, x3], dim=1), out_nhwc=out_nhwc)
+
+
+class DeConv2dBlock(nn.Module):
+    """deconv0 -> dropout -> act -> deconv1 -> act (layers.py:515-559): the block of UpScaler(upsample_mode='conv'), about
+    4x upsampling.  Both layers are nn.ConvTranspose2d(kernel_size=3, stride=2, output_padding) with bias, deconv0 with
+    ``padding`` and deconv1 with max(padding // 2, 1); there is no dropout behind deconv1.  Each layer with what follows
+    it is one operator (ops.conv_transpose3x3s2: a channel product on the GEMM engine + the gather kernel that adds bias,
+    dropout and activation); the nn.ConvTranspose2d / nn.Dropout members hold the parameters and the module tree.
+    Channel counts must be multiples of 4 (NotImplementedError otherwise), kernel_size 3 and stride 2."""
+
+    def __init__(self, in_dim: int, hidden_dim: int, out_dim: int, stride: int = 2, kernel_size: int = 3, padding: int = 2,
+                 output_padding: int = 1, dropout=0.1, activation_type="silu", debug=False):
+        super().__init__()
+        pad1 = max(padding // 2, 1)
+        self.deconv0 = nn.ConvTranspose2d(in_channels=in_dim, out_channels=hidden_dim, kernel_size=kernel_size, stride=stride,
+                                          output_padding=output_padding, padding=padding)
+        self.deconv1 = nn.ConvTranspose2d(in_channels=hidden_dim, out_channels=out_dim, kernel_size=kernel_size,
+                                          stride=stride, output_padding=output_padding, padding=pad1)
+        self.activation = nn.SiLU() if activation_type == "silu" else nn.ReLU()       # (None is ReLU here, layers.py:548)
+        self.dropout = nn.Dropout(dropout)
+        self.debug = debug
+
+    def _deconv(self, layer, x, p_drop):
+        same = lambda v, want: tuple(v) == (want, want)
+        if not (same(layer.kernel_size, 3) and same(layer.stride, 2) and same(layer.dilation, 1) and layer.groups == 1
+                and layer.padding[0] == layer.padding[1] and layer.output_padding[0] == layer.output_padding[1]):
+            raise NotImplementedError("DeConv2dBlock: only ConvTranspose2d(kernel_size=3, stride=2) with square padding has a "
+                                      "HIP path")
+        return ops.conv_transpose3x3s2(x, layer.weight, layer.bias, layer.padding[0], layer.output_padding[0], p_drop,
+                                       _act_name(self.activation), self.training)
+
+    def forward(self, x, in_nhwc=False, out_nhwc=False):
+        """x (B, C, H, W), or (B, H, W, C) with ``in_nhwc``; the operators themselves are channels-last."""
+        H.need_f32_cuda(x)
+        if not in_nhwc:
+            x = x.permute(0, 2, 3, 1)
+        x = self._deconv(self.deconv0, x, self.dropout.p)
+        x = self._deconv(self.deconv1, x, 0.0)
+        return x if out_nhwc else x.permute(0, 3, 1, 2).contiguous()
 
 
 _fuse_act2 = [os.environ.get("GT_CONV_ACT2", "1") != "0"]      # A/B switch: the up-scaler's two SiLUs on the convolution's epilogue

@@ -16,8 +16,8 @@ from torch import nn
 from torch.nn.init import constant_, xavier_uniform_
 
 from . import ops
-from .layers import (FeedForward, Identity, Interp2dEncoder, Interp2dUpsample, PositionalEncoding,
-                     SimpleAttention, SpectralConv1d, SpectralConv2d, _act_module, _act_name, default)
+from .layers import (Conv2dEncoder, DeConv2dBlock, FeedForward, Identity, Interp2dEncoder, Interp2dUpsample,
+                     PositionalEncoding, SimpleAttention, SpectralConv1d, SpectralConv2d, _act_module, _act_name, default)
 
 current_path = os.path.dirname(os.path.abspath(__file__))
 SRC_ROOT = os.path.dirname(current_path)
@@ -214,12 +214,19 @@ class _ToChannelsFirst(torch.autograd.Function):
 
 
 class DownScaler(nn.Module):
-    """(B, n, n, in) -> (B, n_s, n_s, out) with conv + bilinear interpolation (model.py:640-687)."""
+    """(B, n, n, in) -> (B, n_s, n_s, out) (model.py:640-687).  downsample_mode='interp': conv + bilinear interpolation to
+    ``interp_size``.  downsample_mode='conv' (the default): two Conv2dEncoders, the second with ``padding`` -- convolutions and
+    2x2 average pools, n -> n_s fixed by the layers (13, 16, 21, 33, 35 -> 3, 4, 4, 5, 5); ``dropout`` and ``interp_size`` are
+    not used in this mode, as in the reference."""
 
     def __init__(self, in_dim, out_dim, dropout=0.1, padding=5, downsample_mode='conv',
                  activation_type='silu', interp_size=None, debug=False):
         super().__init__()
-        if downsample_mode == 'interp':
+        if downsample_mode == 'conv':
+            self.downsample = nn.Sequential(
+                Conv2dEncoder(in_dim=in_dim, out_dim=out_dim, activation_type=activation_type, debug=debug),
+                Conv2dEncoder(in_dim=out_dim, out_dim=out_dim, padding=padding, activation_type=activation_type, debug=debug))
+        elif downsample_mode == 'interp':
             self.downsample = Interp2dEncoder(in_dim=in_dim, out_dim=out_dim, interp_size=interp_size,
                                               activation_type=activation_type, dropout=dropout, debug=debug)
         else:
@@ -232,17 +239,29 @@ class DownScaler(nn.Module):
         x = x.reshape(bsz, n_grid, n_grid, self.in_dim)
         # one input channel: channels-last and channels-first are the same bytes
         x = x.reshape(bsz, 1, n_grid, n_grid) if self.in_dim == 1 else _ToChannelsFirst.apply(x)
+        if isinstance(self.downsample, nn.Sequential):      # 'conv': the last pool of the second encoder writes channels-last
+            return self.downsample[1](self.downsample[0](x), out_nhwc=True)
         return self.downsample(x, out_nhwc=True)
 
 
 class UpScaler(nn.Module):
-    """(B, n_s, n_s, in) -> (B, n, n, out): interp -> conv -> interp (model.py:690-749)."""
+    """(B, n_s, n_s, in) -> (B, n, n, out) (model.py:690-749).  upsample_mode='interp': interp -> conv -> interp to
+    ``interp_size``.  upsample_mode='conv' / 'deconv' (the default): two DeConv2dBlocks of transposed convolutions, channels-last
+    throughout, n_s -> 16 n_s - 45 with the default padding=2, output_padding=0 (5 -> 35).  As in the reference the second
+    block is built from ``in_dim`` again, so this mode needs out_dim == in_dim."""
 
     def __init__(self, in_dim: int, out_dim: int, hidden_dim=None, padding=2, output_padding=0, dropout=0.1,
                  upsample_mode='conv', activation_type='silu', interp_mode='bilinear', interp_size=None,
                  debug=False):
         super().__init__()
-        if upsample_mode == 'interp':
+        hidden_dim = default(hidden_dim, in_dim)
+        if upsample_mode in ['conv', 'deconv']:
+            self.upsample = nn.Sequential(
+                DeConv2dBlock(in_dim=in_dim, out_dim=out_dim, hidden_dim=hidden_dim, padding=padding,
+                              output_padding=output_padding, dropout=dropout, activation_type=activation_type, debug=debug),
+                DeConv2dBlock(in_dim=in_dim, out_dim=out_dim, hidden_dim=hidden_dim, padding=padding * 2,
+                              output_padding=output_padding, dropout=dropout, activation_type=activation_type, debug=debug))
+        elif upsample_mode == 'interp':
             self.upsample = Interp2dUpsample(in_dim=in_dim, out_dim=out_dim, interp_mode=interp_mode,
                                              interp_size=interp_size, dropout=dropout,
                                              activation_type=activation_type, debug=debug)
@@ -252,6 +271,10 @@ class UpScaler(nn.Module):
         self.out_dim = out_dim
 
     def forward(self, x):
+        if isinstance(self.upsample, nn.Sequential):        # 'conv' / 'deconv'
+            for block in self.upsample:
+                x = block(x, in_nhwc=True, out_nhwc=True)
+            return x
         return self.upsample(x, in_nhwc=True, out_nhwc=True)
 
 

@@ -13,6 +13,8 @@ One module per operator family; this file only re-exports (every name is the obj
                  one statement of the size-or-scale-factor rule
 ``conv``         conv0 + resize, the wide channels-last 3x3 convolution, the chain of three narrow ones; their filter
                  layouts, weight-gradient route, library fallback, eligibility functions and switches
+``scaler_conv`` the 'conv' scaler modes: 2x2 average pool + activation, the 3x3 / stride-2 transposed convolution,
+                 ``deconv_out_size``
 ``dense``        ``packed_params``, Linear, the regression head, FeedForward, FeedForward with BatchNorm1d
 ``loss``         the weighted-L2 / H1 objectives per sample: ``H1Loss2dFn`` (2-D), ``H1Loss1dFn`` (1-D)
 ``attention``    the attention-dropout mode and mask queue, ``SimpleAttentionFn`` with its projection stage and cores,
@@ -35,3 +37,5 @@ from .elementwise import (DropActFn, DropoutFn, LayerNormFn, _c, _next_salt, dro
 from .loss import H1Loss1dFn, H1Loss2dFn, weighted_l2_terms_1d, weighted_l2_terms_2d  # noqa: F401
 from .resize import (ResizeFn, ResizeSegFn, UpsampleFcFn, bilinear_resize, bilinear_resize_seg, out_size,  # noqa: F401
                      upsample_fc)
+from .scaler_conv import (AvgPool2ActFn, ConvTranspose3x3S2Fn, avgpool2_act, conv_transpose3x3s2,  # noqa: F401
+                          deconv_out_size)

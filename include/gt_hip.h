@@ -853,6 +853,54 @@ int gt_h1loss1d_bwd(const float* P, int64_t ldp, const float* T, const float* G,
                     const float* gl, const float* gr, int32_t N, int32_t L, int32_t dilation, float h, float beta,
                     float gamma_h, float* dP, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The 'conv' scaler modes (DownScaler / UpScaler with downsample_mode / upsample_mode = 'conv', model.py:653-662, 709-726;
+ * ABI v21, additive).
+ *
+ * y = act(avgpool2x2(x)): nn.AvgPool2d(2) and the activation behind it in Conv2dEncoder (layers.py:329-341).  x [B,C,H,W]
+ * (in_nhwc = 0) or [B,H,W,C]; y likewise with Ho = H / 2, Wo = W / 2 (floor: an odd trailing row / column is not read) and
+ * out_nhwc.  act: GT_ACT_NONE | GT_ACT_RELU | GT_ACT_SILU.  Backward: dx (x's shape and layout) = 0.25 act'(pooled) dy at the
+ * four contributors, zeros in a dropped row / column; `pooled` is recomputed from x.  Every value is written once, no
+ * atomics.  float4 / float2 accesses where both sides are channels-last with C % 4 == 0, or both channels-first with
+ * W % 4 == 0, and the pointers are 16-byte aligned; scalar ones otherwise.  H < 2, W < 2 or another act: GT_EINVAL.
+ * ------------------------------------------------------------------------------------------- */
+int gt_avgpool2_act_fwd(const float* x, float* y, int32_t B, int32_t C, int32_t H, int32_t W, int32_t in_nhwc,
+                        int32_t out_nhwc, int32_t act, void* stream);
+int gt_avgpool2_act_bwd(const float* x, const float* dy, float* dx, int32_t B, int32_t C, int32_t H, int32_t W,
+                        int32_t in_nhwc, int32_t out_nhwc, int32_t act, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Spatial half of nn.ConvTranspose2d(Cin, Cout, kernel_size=3, stride=2, padding=pad, output_padding=outpad) on channels-last
+ * images (DeConv2dBlock, layers.py:515-559):  y[b,oy,ox,co] = bias[co] + sum x[b,iy,ix,ci] w[ci,co,ky,kx],  oy = 2 iy - pad + ky,
+ * Ho = 2 (H - 1) - 2 pad + 3 + outpad (Wo likewise).  The channel contraction is the caller's gt_gemm product
+ *     cols[(b,iy,ix)][(ky*3 + kx)*Cout + co] = sum_ci x[b,iy,ix,ci] w[ci,co,ky,kx]          dense [B H W][9 Cout]
+ * and these entry points move between cols and the image in gather form (an output row reads the taps ky with
+ * (oy + pad - ky) even and (oy + pad - ky) / 2 in [0, H): at most four of the nine taps per output pixel):
+ *   gt_deconv3x3s2_gather_fwd  y = act(dropout(bias + gathered sum)), dense [B,Ho,Wo,Cout]; the mask index of an element is
+ *                              its index in y.  pre (optional, y's shape): the sum in front of the dropout -- what the
+ *                              backward of GT_ACT_SILU needs.  bias may be NULL.
+ *   gt_deconv3x3s2_gather_bwd  dcols [B H W][9 Cout] = dy * act' * mask gathered the other way, 0 where the tap leaves the
+ *                              image.  gate: `pre` for GT_ACT_SILU, y for GT_ACT_RELU, ignored (may be NULL) for GT_ACT_NONE;
+ *                              the mask is re-drawn from (seed, salt, index).  The caller's products finish the job:
+ *                              dx = dcols W^T, dW = x^T dcols.
+ *   gt_deconv3x3s2_dbias       db[co] = sum over the output pixels of dy * act' * mask; partial rows in ws
+ *                              (>= gt_deconv3x3s2_dbias_ws_bytes), reduced in a fixed order.
+ *   gt_deconv3x3s2_check       0 if the shape is implemented; touches no device.
+ * Each value is written once by one thread in a fixed summation order: no atomics, bit-identical from run to run.  The
+ * caller's stream, no allocation.  Cin % 4 != 0, Cout % 4 != 0 or 2^31 pixels: GT_ENOTSUP; a non-positive size (the output's
+ * included), pad < 0, outpad outside {0, 1}, another act, p outside [0, 1): GT_EINVAL; a pointer off a 16-byte boundary:
+ * GT_EALIGN; ws too small: GT_EWS.
+ * ------------------------------------------------------------------------------------------- */
+int gt_deconv3x3s2_check(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t pad, int32_t outpad);
+int gt_deconv3x3s2_gather_fwd(const float* cols, const float* bias, float* y, float* pre, int32_t B, int32_t H, int32_t W,
+                              int32_t Cout, int32_t pad, int32_t outpad, const gt_dropout* drop, int32_t act, void* stream);
+int gt_deconv3x3s2_gather_bwd(const float* dy, const float* gate, float* dcols, int32_t B, int32_t H, int32_t W, int32_t Cout,
+                              int32_t pad, int32_t outpad, const gt_dropout* drop, int32_t act, void* stream);
+int64_t gt_deconv3x3s2_dbias_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t Cout, int32_t pad, int32_t outpad);
+int gt_deconv3x3s2_dbias(const float* dy, const float* gate, float* db, int32_t B, int32_t H, int32_t W, int32_t Cout,
+                         int32_t pad, int32_t outpad, const gt_dropout* drop, int32_t act, void* ws, int64_t ws_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

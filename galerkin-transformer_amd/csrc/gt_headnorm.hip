@@ -1,146 +1,44 @@
 // Per-head LayerNorm of the Q / K / V projections with the position concat (gfx950): [T][3 h dk] -> head tiles
-// [3][T][h][DP] = [pos(p) | values(dk) | pad], forward and backward, in two generations: the LDS-staged kernels take any
-// shape, the bandwidth-shaped v2 kernels take dk % 4 == 0 with 16-byte aligned operands (head_geom decides).  The backward
-// leaves d(gamma), d(beta) partials per block; gt_slab_reduce sums them in a fixed order.  gt_headtile_* do the same for ONE
-// stream with a row count and a leading dimension of its own (cross-attention: Q rows and K, V rows differ).
+// [3][T][h][DP] = [pos(p) | values(dk) | pad], forward and backward.  gt_headtile_* do the same for ONE stream with a row
+// count and a leading dimension of its own (cross-attention: Q rows and K, V rows differ), for any dk <= 256 and any
+// alignment.  gt_headnorm_* run the bandwidth-shaped v2 kernels, three streams per launch, when dk % 4 == 0, the operands
+// are 16-byte aligned and 3 h G <= 1024 (head_geom decides); otherwise the head-tile kernels, once per stream on column
+// blocks of the caller's buffers.  The backward leaves d(gamma), d(beta) partials per block; gt_slab_reduce sums them in a
+// fixed order.
 #include "gt_common.h"
 
 namespace gt {
 
-// One block handles HN_TOK tokens.  LDS image: seg[tok][3h][dk+1] (pad 1 -> a thread walking its own
-// segment is conflict-free against its neighbours).
-constexpr int HN_TOK_MAX = 16;
-// tokens per block such that the LDS image stays <= ~48 KiB
-static inline int hn_tok(int per_token_floats) {
-    int t = 12000 / std::max(per_token_floats, 1);
-    return std::max(1, std::min(t, HN_TOK_MAX));
+__device__ __forceinline__ float group_sum(float v, int G) {
+    for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
 }
-
-__global__ __launch_bounds__(256) void headnorm_fwd_kernel(
-    const float* __restrict__ qkv, const float* __restrict__ pos, const float* __restrict__ gamma,
-    const float* __restrict__ beta, int T, int h, int dk, int p, int DP, int norm_mask, float eps,
-    float* __restrict__ out, float* __restrict__ stats, int HN_TOK) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int d3 = 3 * h * dk, S = 3 * h, pitch = dk + 1;
-    const int t0 = blockIdx.x * HN_TOK, nt = min(HN_TOK, T - t0);
-    for (int e = threadIdx.x; e < nt * d3; e += blockDim.x) {
-        const int tok = e / d3, f = e % d3;
-        lds[(tok * S + f / dk) * pitch + (f % dk)] = qkv[(int64_t)(t0 + tok) * d3 + f];
-    }
-    __syncthreads();
-    for (int it = threadIdx.x; it < nt * S; it += blockDim.x) {
-        const int tok = it / S, s = it % S, stream = s / h, head = s % h;
-        if (!((norm_mask >> stream) & 1)) continue;
-        int ni = 0;
-        for (int q = 0; q < stream; ++q) ni += (norm_mask >> q) & 1;
-        float* v = lds + it * pitch;
-        float mu = 0.f;
-        for (int j = 0; j < dk; ++j) mu += v[j];
-        mu /= dk;
-        float var = 0.f;
-        for (int j = 0; j < dk; ++j) { const float c = v[j] - mu; var += c * c; }
-        var /= dk;
-        const float rstd = 1.f / sqrtf(var + eps);
-        const float* g = gamma + (ni * h + head) * dk;
-        const float* b = beta + (ni * h + head) * dk;
-        for (int j = 0; j < dk; ++j) v[j] = (v[j] - mu) * rstd * g[j] + b[j];
-        float* st = stats + (((int64_t)ni * T + t0 + tok) * h + head) * 2;
-        st[0] = mu;
-        st[1] = rstd;
-    }
-    __syncthreads();
-    const int per_stream = nt * h * DP;
-    for (int e = threadIdx.x; e < 3 * per_stream; e += blockDim.x) {
-        const int stream = e / per_stream, r = e % per_stream;
-        const int tok = r / (h * DP), head = (r / DP) % h, c = r % DP;
-        float val = 0.f;
-        if (c < p) val = pos[(int64_t)(t0 + tok) * p + c];
-        else if (c < p + dk) val = lds[(tok * S + stream * h + head) * pitch + (c - p)];
-        out[((int64_t)stream * T + t0) * h * DP + r] = val;
-    }
+__device__ __forceinline__ f32x4 keep_first(f32x4 v, int nv) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j >= nv) v[j] = 0.f;
+    return v;
 }
+__device__ __forceinline__ float sum4(f32x4 v) { return v[0] + v[1] + v[2] + v[3]; }
 
-__global__ __launch_bounds__(256) void headnorm_bwd_kernel(
-    const float* __restrict__ d_out, const float* __restrict__ qkv, const float* __restrict__ gamma,
-    const float* __restrict__ stats, int T, int h, int dk, int p, int DP, int norm_mask,
-    float* __restrict__ d_qkv, float* __restrict__ partial /* [nblk][2(dg,db)][2][h][dk] */, int HN_TOK) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int d3 = 3 * h * dk, S = 3 * h, pitch = dk + 1;
-    float* xs = lds;                              // raw -> xhat   [HN_TOK][S][pitch]
-    float* dy = lds + HN_TOK * S * pitch;         // upstream grad [HN_TOK][S][pitch]
-    float* m1 = dy + HN_TOK * S * pitch;          // [HN_TOK*S]
-    float* m2 = m1 + HN_TOK * S;
-    float* rs = m2 + HN_TOK * S;
-    const int ngroups = (T + HN_TOK - 1) / HN_TOK;
-    for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-    const bool first = (grp == (int)blockIdx.x);
-    const int t0 = grp * HN_TOK, nt = min(HN_TOK, T - t0);
-    __syncthreads();
-    for (int e = threadIdx.x; e < nt * d3; e += blockDim.x) {
-        const int tok = e / d3, f = e % d3, s = f / dk, j = f % dk;
-        xs[(tok * S + s) * pitch + j] = qkv[(int64_t)(t0 + tok) * d3 + f];
-        const int stream = s / h, head = s % h;
-        dy[(tok * S + s) * pitch + j] =
-            d_out[(((int64_t)stream * T + t0 + tok) * h + head) * DP + p + j];
-    }
-    __syncthreads();
-    for (int it = threadIdx.x; it < nt * S; it += blockDim.x) {
-        const int tok = it / S, s = it % S, stream = s / h, head = s % h;
-        if (!((norm_mask >> stream) & 1)) continue;
-        int ni = 0;
-        for (int q = 0; q < stream; ++q) ni += (norm_mask >> q) & 1;
-        const float* st = stats + (((int64_t)ni * T + t0 + tok) * h + head) * 2;
-        const float mu = st[0], rstd = st[1];
-        const float* g = gamma + (ni * h + head) * dk;
-        float* x = xs + it * pitch;
-        const float* gy = dy + it * pitch;
-        float a1 = 0.f, a2 = 0.f;
-        for (int j = 0; j < dk; ++j) {
-            const float xh = (x[j] - mu) * rstd;
-            x[j] = xh;
-            const float gg = gy[j] * g[j];
-            a1 += gg;
-            a2 += gg * xh;
-        }
-        m1[it] = a1 / dk;
-        m2[it] = a2 / dk;
-        rs[it] = rstd;
-    }
-    __syncthreads();
-    // dgamma/dbeta partial sums over this block's tokens: one thread per (ni, head, j)
-    const int nn = ((norm_mask & 1) + ((norm_mask >> 1) & 1) + ((norm_mask >> 2) & 1));
-    const int hd = h * dk;
-    float* pg = partial + (int64_t)blockIdx.x * 2 * 2 * hd;
-    for (int e = threadIdx.x; e < 2 * hd; e += blockDim.x) {
-        const int ni = e / hd, head = (e % hd) / dk, j = e % dk;
-        float sg = 0.f, sb = 0.f;
-        if (ni < nn) {
-            int stream = -1, cnt = -1;
-            for (int q = 0; q < 3; ++q)
-                if ((norm_mask >> q) & 1) { if (++cnt == ni) { stream = q; break; } }
-            const int s = stream * h + head;
-            for (int tok = 0; tok < nt; ++tok) {
-                const float gyv = dy[(tok * S + s) * pitch + j];
-                sg += gyv * xs[(tok * S + s) * pitch + j];
-                sb += gyv;
-            }
-        }
-        pg[e] = first ? sg : pg[e] + sg;
-        pg[2 * hd + e] = first ? sb : pg[2 * hd + e] + sb;
-    }
-    for (int e = threadIdx.x; e < nt * d3; e += blockDim.x) {
-        const int tok = e / d3, f = e % d3, s = f / dk, j = f % dk, stream = s / h, head = s % h;
-        const int it = tok * S + s;
-        float g = dy[it * pitch + j];
-        if ((norm_mask >> stream) & 1) {
-            int ni = 0;
-            for (int q = 0; q < stream; ++q) ni += (norm_mask >> q) & 1;
-            const float gm = gamma[(ni * h + head) * dk + j];
-            g = rs[it] * (g * gm - m1[it] - xs[it * pitch + j] * m2[it]);
-        }
-        d_qkv[(int64_t)(t0 + tok) * d3 + f] = g;
-    }
-    }   // token groups
+// The per-row LayerNorm of one head segment spread over G lanes (x: this lane's floats, zeros past nv), stated once for the
+// kernels below.  Forward: the centred values, with *mu and *rstd.
+__device__ __forceinline__ f32x4 seg_center(f32x4 x, int nv, int G, float inv, float eps, float* mu, float* rstd) {
+    *mu = group_sum(sum4(x), G) * inv;
+    const f32x4 c = keep_first(x - *mu, nv);
+    const float var = group_sum(sum4(c * c), G) * inv;
+    *rstd = 1.f / sqrtf(var + eps);
+    return c;
+}
+// Backward from the saved (mu, rstd): dx = rstd * (gy g - mean(gy g) - xh mean(gy g xh)); *xh_out for d(gamma).
+__device__ __forceinline__ f32x4 seg_norm_bwd(f32x4 x, f32x4 gy, f32x4 gm, int nv, int G, float inv, float mu, float rstd,
+                                              f32x4* xh_out) {
+    const f32x4 xh = keep_first((x - mu) * rstd, nv);
+    const f32x4 gg = gy * gm;
+    const float m1 = group_sum(sum4(gg), G) * inv;
+    const float m2 = group_sum(sum4(gg * xh), G) * inv;
+    *xh_out = xh;
+    return rstd * (gg - m1 - xh * m2);
 }
 
 // ---- bandwidth-shaped head norm (dk % 4 == 0) ------------------------------------------------------
@@ -152,11 +50,6 @@ __global__ __launch_bounds__(256) void headnorm_bwd_kernel(
 struct HeadGeom {
     int T, h, dk, p, DP, norm_mask, G, PT, R, tpb;
 };
-
-__device__ __forceinline__ float group_sum(float v, int G) {
-    for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __global__ void headnorm_fwd_v2_kernel(const float* __restrict__ qkv, const float* __restrict__ pos,
                                        const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -192,12 +85,8 @@ __global__ void headnorm_fwd_v2_kernel(const float* __restrict__ qkv, const floa
             const f32x4 x = xx[u];
             f32x4 y = x;
             if (normed) {
-                const float mu = group_sum(x[0] + x[1] + x[2] + x[3], g.G) * inv;
-                f32x4 c = x - mu;
-                if (!active) c = f32x4{0.f, 0.f, 0.f, 0.f};
-                const float var = group_sum(c[0] * c[0] + c[1] * c[1] + c[2] * c[2] + c[3] * c[3], g.G) * inv;
-                const float rstd = 1.f / sqrtf(var + eps);
-                y = c * rstd * gm + bt;
+                float mu, rstd;
+                y = seg_center(x, active ? 4 : 0, g.G, inv, eps, &mu, &rstd) * rstd * gm + bt;
                 if (q == 0)
                     *reinterpret_cast<f32x2*>(stats + (((int64_t)ni * g.T + tt) * g.h + head) * 2) = f32x2{mu, rstd};
             }
@@ -251,13 +140,8 @@ __global__ void headnorm_bwd_v2_kernel(const float* __restrict__ d_out, const fl
                 const f32x4 gy = gyy[u], x = xx[u];
                 f32x4 dx = gy;
                 if (normed) {
-                    const float mu = stt[u][0], rstd = stt[u][1];
-                    f32x4 xh = (x - mu) * rstd;
-                    if (!active) xh = f32x4{0.f, 0.f, 0.f, 0.f};
-                    const f32x4 gg = gy * gm;
-                    const float m1 = group_sum(gg[0] + gg[1] + gg[2] + gg[3], g.G) * inv;
-                    const float m2 = group_sum(gg[0] * xh[0] + gg[1] * xh[1] + gg[2] * xh[2] + gg[3] * xh[3], g.G) * inv;
-                    dx = rstd * (gg - m1 - xh * m2);
+                    f32x4 xh;
+                    dx = seg_norm_bwd(x, gy, gm, active ? 4 : 0, g.G, inv, stt[u][0], stt[u][1], &xh);
                     dg += gy * xh;
                     db += gy;
                 }
@@ -311,7 +195,7 @@ static bool head_geom(int T, int h, int dk, int p, int norm_mask, int max_blocks
     return true;
 }
 
-// ---- single-stream head tiles (cross-attention) ------------------------------------------------------
+// ---- single-stream head tiles (cross-attention; every shape the kernels above do not take) ----------------------------
 // One stream of the above on its own row count: X [T][ldx] (a column block of a wider projection buffer) -> out [T][h][DP]
 // = [pos | values | zero pad], stats [T][h][2]; gamma == NULL: no norm.  The lane layout of the v2 kernels with PT = h*G
 // lanes per token: a lane owns the floats 4q .. 4q+3 of its head segment for the whole kernel.  VEC (dk % 4 == 0, 16-byte
@@ -339,33 +223,6 @@ __device__ __forceinline__ void lane_store(float* __restrict__ dst, int nv, f32x
         for (int j = 0; j < 4; ++j)
             if (j < nv) dst[j] = v[j];
     }
-}
-__device__ __forceinline__ f32x4 keep_first(f32x4 v, int nv) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (j >= nv) v[j] = 0.f;
-    return v;
-}
-__device__ __forceinline__ float sum4(f32x4 v) { return v[0] + v[1] + v[2] + v[3]; }
-
-// The per-row LayerNorm of one head segment spread over G lanes (x: this lane's floats, zeros past nv), stated once for the
-// two kernels below.  Forward: the centred values, with *mu and *rstd.
-__device__ __forceinline__ f32x4 seg_center(f32x4 x, int nv, int G, float inv, float eps, float* mu, float* rstd) {
-    *mu = group_sum(sum4(x), G) * inv;
-    const f32x4 c = keep_first(x - *mu, nv);
-    const float var = group_sum(sum4(c * c), G) * inv;
-    *rstd = 1.f / sqrtf(var + eps);
-    return c;
-}
-// Backward from the saved (mu, rstd): dx = rstd * (gy g - mean(gy g) - xh mean(gy g xh)); *xh_out for d(gamma).
-__device__ __forceinline__ f32x4 seg_norm_bwd(f32x4 x, f32x4 gy, f32x4 gm, int nv, int G, float inv, float mu, float rstd,
-                                              f32x4* xh_out) {
-    const f32x4 xh = keep_first((x - mu) * rstd, nv);
-    const f32x4 gg = gy * gm;
-    const float m1 = group_sum(sum4(gg), G) * inv;
-    const float m2 = group_sum(sum4(gg * xh), G) * inv;
-    *xh_out = xh;
-    return rstd * (gg - m1 - xh * m2);
 }
 
 template <bool VEC>
@@ -480,9 +337,7 @@ static bool stream_geom(int T, int h, int dk, int p, int64_t ldx, int64_t lddx, 
     return true;
 }
 
-static inline int hn_tok_bwd(int h, int dk) { return hn_tok(2 * 3 * h * (dk + 1) + 9 * h); }
 constexpr int HN_MAXB = 1024;      // bound on blocks (= dgamma/dbeta partials) of the backward
-static inline int hn_blocks_bwd(int T, int h, int dk) { return std::min(ceil_div(T, hn_tok_bwd(h, dk)), HN_MAXB); }
 
 }  // namespace gt
 
@@ -495,7 +350,6 @@ extern "C" int gt_headnorm_fwd(const float* qkv, const float* pos, const float* 
     if (p > 0 && !pos) return GT_EINVAL;
     if (norm_mask & ~7) return GT_EINVAL;
     if (norm_mask && (!gamma || !beta || !stats)) return GT_EINVAL;
-    const int DP = round4(dk + p);
     HeadGeom g; int thr, nblk;
     if (!misaligned16(qkv, out, gamma, beta, stats) && head_geom(T, h, dk, p, norm_mask, 1 << 20, &g, &thr, &nblk)) {
         hipLaunchKernelGGL(headnorm_fwd_v2_kernel, dim3(nblk), dim3(thr), 0, (hipStream_t)stream, qkv, pos,
@@ -503,18 +357,22 @@ extern "C" int gt_headnorm_fwd(const float* qkv, const float* pos, const float* 
         GT_LAUNCH_CHECK();
         return 0;
     }
-    const int tok = hn_tok(3 * h * (dk + 1));
-    const size_t lds = (size_t)tok * 3 * h * (dk + 1) * sizeof(float);
-    if (lds > 64 * 1024) return GT_ENOTSUP;
-    hipLaunchKernelGGL(headnorm_fwd_kernel, dim3(ceil_div(T, tok)), dim3(256), lds, (hipStream_t)stream,
-                       qkv, pos, gamma, beta, T, h, dk, p, DP, norm_mask, eps, out, stats, tok);
-    GT_LAUNCH_CHECK();
+    // stream s: the column block s of qkv into the tile block s of out; ni counts the normalised streams below it
+    const int64_t hd = (int64_t)h * dk, tile = (int64_t)T * h * round4(dk + p), st = (int64_t)T * h * 2;
+    for (int s = 0, ni = 0; s < 3; ++s) {
+        const bool normed = (norm_mask >> s) & 1;
+        if (int rc = gt_headtile_fwd(qkv + s * hd, 3 * hd, pos, normed ? gamma + ni * hd : nullptr,
+                                     normed ? beta + ni * hd : nullptr, T, h, dk, p, eps, out + s * tile,
+                                     normed ? stats + ni * st : nullptr, stream))
+            return rc;
+        ni += normed;
+    }
     return 0;
 }
 
 extern "C" int64_t gt_headnorm_bwd_ws_bytes(int32_t T, int32_t h, int32_t dk) {
     (void)T;
-    return (int64_t)HN_MAXB * 4 * h * dk * (int64_t)sizeof(float);      // upper bound for both kernels
+    return (int64_t)HN_MAXB * 4 * h * dk * (int64_t)sizeof(float);      // v2's partials; twice one head-tile stream's
 }
 
 extern "C" int gt_headnorm_bwd(const float* d_out, const float* qkv, const float* gamma, const float* stats,
@@ -524,29 +382,34 @@ extern "C" int gt_headnorm_bwd(const float* d_out, const float* qkv, const float
     if (norm_mask & ~7) return GT_EINVAL;
     if (norm_mask && (!gamma || !stats || !dgamma || !dbeta)) return GT_EINVAL;
     if (!ws || ws_bytes < gt_headnorm_bwd_ws_bytes(T, h, dk)) return GT_EWS;
-    const int DP = round4(dk + p);
-    const int S = 3 * h;
-    const int tok = hn_tok_bwd(h, dk);
-    const size_t lds = ((size_t)2 * tok * S * (dk + 1) + 3 * tok * S) * sizeof(float);
-    int nblk = hn_blocks_bwd(T, h, dk);
-    float* partial = reinterpret_cast<float*>(ws);
-    HeadGeom g; int thr, nb2;
-    if (!misaligned16(qkv, d_qkv, gamma, stats, d_out) && head_geom(T, h, dk, p, norm_mask, HN_MAXB, &g, &thr, &nb2)) {
-        nblk = nb2;
-        const size_t lds2 = (size_t)g.R * g.PT * 8 * sizeof(float);
-        hipLaunchKernelGGL(headnorm_bwd_v2_kernel, dim3(nblk), dim3(thr), lds2, (hipStream_t)stream, d_out,
+    const int64_t hd = (int64_t)h * dk;
+    HeadGeom g; int thr, nblk;
+    if (!misaligned16(qkv, d_qkv, gamma, stats, d_out) && head_geom(T, h, dk, p, norm_mask, HN_MAXB, &g, &thr, &nblk)) {
+        float* partial = reinterpret_cast<float*>(ws);      // [nblk][ (dg: 2*hd) | (db: 2*hd) ]
+        const size_t lds = (size_t)g.R * g.PT * 8 * sizeof(float);
+        hipLaunchKernelGGL(headnorm_bwd_v2_kernel, dim3(nblk), dim3(thr), lds, (hipStream_t)stream, d_out,
                            qkv, gamma, stats, g, d_qkv, partial);
-    } else {
-        if (lds > 64 * 1024) return GT_ENOTSUP;
-        hipLaunchKernelGGL(headnorm_bwd_kernel, dim3(nblk), dim3(256), lds, (hipStream_t)stream, d_out, qkv,
-                           gamma, stats, T, h, dk, p, DP, norm_mask, d_qkv, partial, tok);
-    }
-    GT_LAUNCH_CHECK();
-    if (norm_mask) {
-        const int hd = h * dk;
-        // partial: [nblk][ (dg: 2*hd) | (db: 2*hd) ]
+        GT_LAUNCH_CHECK();
+        if (!norm_mask) return 0;
         if (int rc = gt_slab_reduce(partial, 4 * hd, nblk, 2 * hd, 1.f, dgamma, stream)) return rc;
         return gt_slab_reduce(partial + 2 * hd, 4 * hd, nblk, 2 * hd, 1.f, dbeta, stream);
+    }
+    // per stream as in the forward; the streams run in order on `stream`, so each reuses ws for its partials
+    const int64_t tile = (int64_t)T * h * round4(dk + p), st = (int64_t)T * h * 2;
+    int ni = 0;
+    for (int s = 0; s < 3; ++s) {
+        const bool normed = (norm_mask >> s) & 1;
+        if (int rc = gt_headtile_bwd(d_out + s * tile, qkv + s * hd, 3 * hd, normed ? gamma + ni * hd : nullptr,
+                                     normed ? stats + ni * st : nullptr, T, h, dk, p, d_qkv + s * hd, 3 * hd,
+                                     normed ? dgamma + ni * hd : nullptr, normed ? dbeta + ni * hd : nullptr, ws,
+                                     ws_bytes, stream))
+            return rc;
+        ni += normed;
+    }
+    if (ni == 1) {      // the slot with no stream reads zero, as from the kernel above
+        hipError_t e = hipMemsetAsync(dgamma + hd, 0, hd * sizeof(float), (hipStream_t)stream);
+        if (e == hipSuccess) e = hipMemsetAsync(dbeta + hd, 0, hd * sizeof(float), (hipStream_t)stream);
+        if (e != hipSuccess) return (int)e;
     }
     return 0;
 }

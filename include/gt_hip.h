@@ -320,7 +320,11 @@ int gt_slab_reduce(const float* slabs, int64_t stride, int32_t n_slabs, int64_t 
  *              Q,K = 3; no attn norm: 0)
  *   out   [3][T][h][DP]  with DP = round_up(dk+p, 4); columns [0,p) = pos, [p,p+dk) = values,
  *                        rest zero.  stats [2][T][h][2] = (mean, rstd) of the normalised streams.
- * Backward: d_out -> d_qkv [T,3d], dgamma/dbeta [2][h][dk] (deterministic two-pass).
+ * Backward: d_out -> d_qkv [T,3d], dgamma/dbeta [2][h][dk] (deterministic two-pass); with norm_mask != 0 both slots
+ *   are written, a slot with no stream as zero; with norm_mask == 0 neither is touched and qkv is not read.
+ * dk % 4 == 0 with 16-byte aligned operands and 3 * h * pow2(dk / 4) <= 1024 runs the three streams in one launch;
+ * anything else runs the gt_headtile_* kernels below once per stream, within their limits: dk <= 256 and
+ * h * pow2(ceil(dk / 4)) <= 1024, else GT_ENOTSUP.
  * ------------------------------------------------------------------------------------------- */
 int gt_headnorm_fwd(const float* qkv, const float* pos, const float* gamma, const float* beta,
                     int32_t T, int32_t h, int32_t dk, int32_t p, int32_t norm_mask, float eps,

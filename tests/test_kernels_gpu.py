@@ -203,11 +203,9 @@ def _headnorm_ref(qkv, pos, gamma, beta, h, dk, p, norm_mask, eps):
     return torch.stack(outs)
 
 
-@pytest.mark.parametrize("h,dk,p,mask", [(4, 32, 2, 6), (4, 16, 1, 3), (1, 96, 1, 6), (2, 48, 2, 6),
-                                         (1, 48, 2, 0)])
-def test_headnorm_fwd_bwd(H, gpu_device, h, dk, p, mask):
-    dev = gpu_device
-    T, eps = 1003, 1e-7
+def _headnorm_case(H, dev, T, h, dk, p, mask, eps=1e-7):
+    """One forward and backward of H.headnorm_* against the float64 reference, at the suite's gates."""
+    DP = (dk + p + 3) // 4 * 4
     qkv = rnd(T, 3 * h * dk, dev=dev, seed=24)
     pos = torch.rand(T, p, device=dev)
     gamma = 1 + 0.1 * rnd(2, h, dk, dev=dev, seed=25)
@@ -218,15 +216,78 @@ def test_headnorm_fwd_bwd(H, gpu_device, h, dk, p, mask):
     ref = _headnorm_ref(q64, pos.double(), g64, b64, h, dk, p, mask, eps)
     torch.cuda.synchronize()
     assert rel_l2(out, ref) < KTOL
+    assert torch.equal(out[..., p + dk:], torch.zeros(3, T, h, DP - dk - p, device=dev)), "pad columns"
+    assert torch.equal(out[..., :p], pos[None, :, None, :].expand(3, T, h, p)), "coordinate columns"
     cot = rnd(*out.shape, dev=dev, seed=27)
     dq, dg, db = H.headnorm_bwd(cot, qkv, gamma, stats, T, h, dk, p, mask)
     torch.cuda.synchronize()
     grads = torch.autograd.grad(ref, [q64, g64, b64], cot.double(), allow_unused=True)
     assert rel_l2(dq, grads[0]) < 5 * KTOL
+    nn_ = bin(mask).count("1")
     if mask:
-        nn_ = bin(mask).count("1")
         assert rel_l2(dg[:nn_], grads[1][:nn_]) < 5 * KTOL
         assert rel_l2(db[:nn_], grads[2][:nn_]) < 5 * KTOL
+    if nn_ == 1:          # the slot with no stream behind it
+        assert not dg[1].any() and not db[1].any()
+    if not mask:          # no norm: a copy forward, a scatter backward
+        assert torch.equal(out[..., p:p + dk], qkv.reshape(T, 3, h, dk).transpose(0, 1))
+        assert torch.equal(dq.reshape(T, 3, h, dk), cot[..., p:p + dk].transpose(0, 1))
+
+
+# The first five run the three-stream kernels.  The rest are what those do not take, and run the head-tile kernels per stream:
+# dk % 4 != 0 with a last lane of 2 / 1 / 3 floats, with and without coordinates, two streams with and without a gap between
+# them, one stream, none; and dk % 4 == 0 with 3 h G = 1536 lanes per token (the float4 head-tile kernels).
+@pytest.mark.parametrize("h,dk,p,mask", [(4, 32, 2, 6), (4, 16, 1, 3), (1, 96, 1, 6), (2, 48, 2, 6),
+                                         (1, 48, 2, 0),
+                                         (3, 10, 1, 6), (2, 6, 0, 3), (1, 33, 2, 5), (2, 6, 0, 2), (5, 7, 3, 0),
+                                         (16, 96, 1, 6)])
+def test_headnorm_fwd_bwd(H, gpu_device, h, dk, p, mask):
+    for T in (1, 1003):          # one block; several blocks of partials
+        _headnorm_case(H, gpu_device, T, h, dk, p, mask)
+
+
+@pytest.mark.parametrize("T", [17, 1003])
+@pytest.mark.parametrize("h,dk,p,mask,off", [(3, 10, 1, 6, 0), (2, 8, 2, 3, 1)])
+def test_headnorm_fallback_is_headtile_per_stream(H, gpu_device, h, dk, p, mask, off, T):
+    """Off the three-stream kernels (dk % 4 != 0; qkv one float off a 16-byte boundary) headnorm_* is headtile_* on the
+    three column blocks: the same kernels on the same pointers, so every output is identical."""
+    dev, hd, eps = gpu_device, h * dk, 1e-7
+    qkv = rnd(T * 3 * hd + off, dev=dev, seed=31)[off:].view(T, 3 * hd)
+    assert qkv.data_ptr() % 16 == 4 * off
+    pos = torch.rand(T, p, device=dev)
+    gamma = 1 + 0.1 * rnd(2, h, dk, dev=dev, seed=32)
+    beta = 0.1 * rnd(2, h, dk, dev=dev, seed=33)
+    out, stats = H.headnorm_fwd(qkv, pos, gamma, beta, T, h, dk, p, mask, eps)
+    cot = rnd(*out.shape, dev=dev, seed=34)
+    dq, dg, db = H.headnorm_bwd(cot, qkv, gamma, stats, T, h, dk, p, mask)
+    dq2 = torch.empty_like(dq)
+    dg2, db2 = torch.zeros_like(dg), torch.zeros_like(db)
+    ni = 0
+    for s in range(3):
+        X, normed = qkv[:, s * hd:], bool((mask >> s) & 1)
+        gm, bt = (gamma[ni], beta[ni]) if normed else (None, None)
+        tiles, st = H.headtile_fwd(X, 3 * hd, pos, gm, bt, T, h, dk, p, eps)
+        assert torch.equal(out[s], tiles), s
+        if normed:
+            assert torch.equal(stats[ni], st), s
+        H.headtile_bwd(cot[s], X, 3 * hd, gm, st, T, h, dk, p, dq2[:, s * hd:], 3 * hd,
+                       dg2[ni] if normed else None, db2[ni] if normed else None)
+        ni += normed
+    torch.cuda.synchronize()
+    assert torch.equal(dq, dq2) and torch.equal(dg, dg2) and torch.equal(db, db2)
+
+
+def test_headnorm_refuses_heads_wider_than_256(H, gpu_device):
+    """dk = 260 is past the head-tile kernels' lanes: GT_ENOTSUP from both entry points before any launch."""
+    lib, st, T, dk = H.lib(), H.stream_ptr(), 4, 260
+    x, o, g = (torch.zeros(n, device=gpu_device) for n in (T * 3 * dk, 3 * T * dk, 2 * dk))
+    stats = torch.zeros(2 * T * 2, device=gpu_device)
+    ws = torch.zeros(lib.gt_headnorm_bwd_ws_bytes(T, 1, dk) // 4, device=gpu_device)
+    assert lib.gt_headnorm_fwd(x.data_ptr(), None, g.data_ptr(), g.data_ptr(), T, 1, dk, 0, 6, 1e-5, o.data_ptr(),
+                               stats.data_ptr(), st) == -4
+    assert lib.gt_headnorm_bwd(o.data_ptr(), x.data_ptr(), g.data_ptr(), stats.data_ptr(), T, 1, dk, 0, 6, x.data_ptr(),
+                               g.data_ptr(), g.data_ptr(), ws.data_ptr(), ws.numel() * 4, st) == -4
+    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("B,h,dk,p,d", [(2, 4, 32, 2, 128), (1, 1, 96, 1, 96), (3, 2, 48, 2, 96)])

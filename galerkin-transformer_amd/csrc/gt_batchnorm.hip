@@ -6,12 +6,11 @@
 //                                     running_var  <- (1 - m) running_var  + m var T / (T - 1)
 // eval    : mean / var are the running buffers, nothing is updated, and the backward has no mean terms.
 //
-// The matrix is a dense [T][C4] array of float4 (C4 = f / 4).  A block owns `chunk` consecutive rows and CG <= 256 adjacent
-// column groups (whole 64-byte runs per row and more); its threads form RL = 256 / CG row lanes.
-//     forward : partial   per (chunk, column): Welford (mean, M2) per row lane, lanes merged in lane order; the values are
-//                         taken relative to row 0 of the column (a pivot common to all partials), so a large common offset
-//                         costs the running means no digits
-//               group     per (group of BN_GROUP chunks, column): the chunks merged in chunk order (Chan's pairwise update)
+// The matrix is a dense [T][C4] array of float4 (C4 = f / 4) and the passes are the column-statistics passes of gt_colpass.h,
+// which states the block shape, the Welford / pivot / Chan arithmetic and the merge orders: a block owns `chunk` consecutive
+// rows and CG <= 256 adjacent column groups; its threads form RL = 256 / CG row lanes.
+//     forward : partial   per (chunk, column): (mean, M2) relative to row 0 of the column
+//               group     per (group of BN_GROUP chunks, column): the chunks merged in chunk order
 //               finalize  per column: the groups merged in group order, pivot added back once -> stats, bvar, running buffers
 //               apply     z = (x - mean) * (rstd gamma) + beta
 //     eval    : stats     from the running buffers, then the same apply
@@ -21,36 +20,25 @@
 //                         and dropout in front of the norm, stored once
 // The chunk length follows T: short chunks while the blocks would not cover the device, longer ones so that there are never
 // more than BN_MAX_CHUNKS of them, hence at most BN_MAX_CHUNKS / BN_GROUP groups for the last, single-thread merge.
-// The variance is never formed as E[x^2] - mean^2.  No atomics, every merge in a fixed order: two runs give the same bits.
 // In place is allowed (Z == X, dX == dZ): the statistics are complete before the applying launch starts, and there every
 // thread reads the elements it owns before it writes them.
 #include <math.h>
 
-#include <algorithm>
-
-#include "gt_common.h"
+#include "gt_colpass.h"
 
 namespace gt {
 namespace {
 
-constexpr int BN_THREADS = 256;
-constexpr int BN_CHUNK_START = 128, BN_CHUNK_MIN = 32;
-constexpr int BN_MIN_BLOCKS = 1024;      // four blocks per CU of the 256 before the chunks stop shrinking
 constexpr int BN_MAX_CHUNKS = 4096;      // longer chunks beyond: the merges stay short whatever T is
 constexpr int BN_GROUP = 64;             // chunks per group: the first merge level
 
-struct BnGeom {
-    int C4, CG, RL, ncb, nchunks, ngroups;
+struct BnGeom : ColGeom {
+    int nchunks, ngroups;
     int64_t chunk;
 };
 static inline BnGeom bn_geom(int64_t T, int f) {
-    BnGeom g;
-    g.C4 = f / 4;
-    g.CG = std::min(g.C4, BN_THREADS);
-    g.RL = BN_THREADS / g.CG;
-    g.ncb = (g.C4 + g.CG - 1) / g.CG;
-    g.chunk = BN_CHUNK_START;
-    while (g.chunk > BN_CHUNK_MIN && ((T + g.chunk - 1) / g.chunk) * g.ncb < BN_MIN_BLOCKS) g.chunk >>= 1;
+    BnGeom g{col_geom(f / 4), 0, 0, 0};
+    g.chunk = col_chunk(T, g.ncb);
     while ((T + g.chunk - 1) / g.chunk > BN_MAX_CHUNKS) g.chunk <<= 1;
     g.nchunks = (int)((T + g.chunk - 1) / g.chunk);
     g.ngroups = (g.nchunks + BN_GROUP - 1) / BN_GROUP;
@@ -81,18 +69,6 @@ struct BnP {
     DropDev drop;
 };
 
-__host__ __device__ __forceinline__ int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
-
-// (mean, M2, na) <- merged with (mb, Mb, nb): Chan et al.'s pairwise update.  na == 0 gives (mb, Mb) exactly.
-__device__ __forceinline__ void bn_merge(f32x4& mean, f32x4& M2, float& na, const f32x4 mb, const f32x4 Mb, const float nb) {
-    if (nb == 0.f) return;
-    const float nt = na + nb, w = nb / nt;
-    const f32x4 d = mb - mean;
-    mean += d * w;
-    M2 += Mb + d * d * (na * w);
-    na = nt;
-}
-
 // (mean, rstd) of the four columns of group col4 from stats [f][2]
 __device__ __forceinline__ void bn_load_stats(const BnP& p, int col4, f32x4& mean, f32x4& rstd) {
     const f32x4 a = reinterpret_cast<const f32x4*>(p.stats)[2 * col4], b = reinterpret_cast<const f32x4*>(p.stats)[2 * col4 + 1];
@@ -105,56 +81,25 @@ __device__ __forceinline__ void bn_store_stats(const BnP& p, int col4, const f32
 }
 
 template <bool BWD>
-__global__ __launch_bounds__(BN_THREADS) void batchnorm_partial_kernel(BnP p) {
-    __shared__ f32x4 sa[BN_THREADS], sb[BN_THREADS];
-    const int t = threadIdx.x;
-    const int cl = t % p.CG, rl = t / p.CG;
-    const int col4 = blockIdx.y * p.CG + cl;
+__global__ __launch_bounds__(COL_THREADS) void batchnorm_partial_kernel(BnP p) {
+    __shared__ f32x4 sa[COL_THREADS], sb[COL_THREADS];
+    const ColLane L = col_lane(p.CG, p.RL, p.C4, blockIdx.y);
     const int chunk = blockIdx.x;
-    const bool active = rl < p.RL && col4 < p.C4;
-    const int64_t row0 = chunk * p.chunk, row1 = min64(p.T, row0 + p.chunk);
+    const ColRows<int64_t> R = col_rows(chunk, p.chunk, p.T);
     f32x4 a = {0.f, 0.f, 0.f, 0.f}, m2 = {0.f, 0.f, 0.f, 0.f};      // fwd: (mean, M2) ; bwd: (s1, s2)
-    if (active) {
-        const f32x4* X4 = reinterpret_cast<const f32x4*>(p.X) + col4;
+    if (L.active) {
+        const f32x4* X4 = reinterpret_cast<const f32x4*>(p.X) + L.col4;      // row 0: the pivot row
         if (BWD) {
-            const f32x4* G4 = reinterpret_cast<const f32x4*>(p.G) + col4;
             f32x4 mean, rstd;
-            bn_load_stats(p, col4, mean, rstd);
-#pragma unroll 4
-            for (int64_t r = row0 + rl; r < row1; r += p.RL) {
-                const f32x4 x = X4[r * p.C4], g = G4[r * p.C4];
-                a += g;
-                m2 += g * ((x - mean) * rstd);
-            }
+            bn_load_stats(p, L.col4, mean, rstd);
+            col_gsum_rows(X4, reinterpret_cast<const f32x4*>(p.G) + L.col4, p.C4, R.r0 + L.rl, R.r1, p.RL, mean, rstd, a, m2);
         } else {
-            const f32x4 piv = X4[0];      // row 0: every partial of a column is taken relative to it
-            float cnt = 0.f;
-#pragma unroll 4
-            for (int64_t r = row0 + rl; r < row1; r += p.RL) {
-                const f32x4 x = X4[r * p.C4] - piv;
-                cnt += 1.f;
-                const f32x4 d = x - a;
-                a += d * (1.f / cnt);
-                m2 += d * (x - a);
-            }
+            col_welford_rows(X4, p.C4, R.r0 + L.rl, R.r1, p.RL, a, m2);
         }
     }
-    sa[t] = a;
-    sb[t] = m2;
-    __syncthreads();
-    if (active && rl == 0) {
-        const int64_t rows = row1 - row0;
-        float na = (float)((rows + p.RL - 1) / p.RL);      // rows of lane 0; lane q has (rows - q + RL - 1) / RL
-        for (int q = 1; q < p.RL; ++q) {
-            const f32x4 a2 = sa[q * p.CG + cl], b2 = sb[q * p.CG + cl];
-            if (BWD) {
-                a += a2;
-                m2 += b2;
-            } else {
-                bn_merge(a, m2, na, a2, b2, q < rows ? (float)((rows - q + p.RL - 1) / p.RL) : 0.f);
-            }
-        }
-        f32x4* o = p.part + (int64_t)chunk * 2 * p.C4 + col4;
+    col_merge_lanes<BWD>(sa, sb, L, p.CG, p.RL, R.r1 - R.r0, a, m2);
+    if (L.active && L.rl == 0) {
+        f32x4* o = p.part + (int64_t)chunk * 2 * p.C4 + L.col4;
         o[0] = a;
         o[p.C4] = m2;
     }
@@ -162,23 +107,13 @@ __global__ __launch_bounds__(BN_THREADS) void batchnorm_partial_kernel(BnP p) {
 
 // first merge level, one thread per (group, column group): the group's chunks in chunk order
 template <bool BWD>
-__global__ __launch_bounds__(BN_THREADS) void batchnorm_group_kernel(BnP p) {
-    const int64_t idx = (int64_t)blockIdx.x * BN_THREADS + threadIdx.x;
+__global__ __launch_bounds__(COL_THREADS) void batchnorm_group_kernel(BnP p) {
+    const int64_t idx = (int64_t)blockIdx.x * COL_THREADS + threadIdx.x;
     if (idx >= (int64_t)p.ngroups * p.C4) return;
     const int grp = (int)(idx / p.C4), col4 = (int)(idx - (int64_t)grp * p.C4);
     const int q0 = grp * BN_GROUP, q1 = min(p.nchunks, q0 + BN_GROUP);
     f32x4 a = {0.f, 0.f, 0.f, 0.f}, m2 = {0.f, 0.f, 0.f, 0.f};
-    float na = 0.f;
-    for (int q = q0; q < q1; ++q) {
-        const f32x4* o = p.part + (int64_t)q * 2 * p.C4 + col4;
-        const f32x4 a2 = o[0], b2 = o[p.C4];
-        if (BWD) {
-            a += a2;
-            m2 += b2;
-        } else {
-            bn_merge(a, m2, na, a2, b2, (float)(min64(p.T, (q + 1) * p.chunk) - q * p.chunk));
-        }
-    }
+    col_merge_chunks<BWD>(p.part + col4, p.C4, q0, q1, p.chunk, p.T, a, m2);
     f32x4* o = p.gpart + (int64_t)grp * 2 * p.C4 + col4;
     o[0] = a;
     o[p.C4] = m2;
@@ -186,22 +121,11 @@ __global__ __launch_bounds__(BN_THREADS) void batchnorm_group_kernel(BnP p) {
 
 // second merge level, one thread per column group: the groups in group order, then what hangs on the column totals
 template <bool BWD>
-__global__ __launch_bounds__(BN_THREADS) void batchnorm_finalize_kernel(BnP p) {
-    const int col4 = blockIdx.x * BN_THREADS + threadIdx.x;
+__global__ __launch_bounds__(COL_THREADS) void batchnorm_finalize_kernel(BnP p) {
+    const int col4 = blockIdx.x * COL_THREADS + threadIdx.x;
     if (col4 >= p.C4) return;
-    const int64_t grows = (int64_t)BN_GROUP * p.chunk;
     f32x4 a = {0.f, 0.f, 0.f, 0.f}, m2 = {0.f, 0.f, 0.f, 0.f};
-    float na = 0.f;
-    for (int g = 0; g < p.ngroups; ++g) {
-        const f32x4* o = p.gpart + (int64_t)g * 2 * p.C4 + col4;
-        const f32x4 a2 = o[0], b2 = o[p.C4];
-        if (BWD) {
-            a += a2;
-            m2 += b2;
-        } else {
-            bn_merge(a, m2, na, a2, b2, (float)(min64(p.T, (g + 1) * grows) - g * grows));
-        }
-    }
+    col_merge_chunks<BWD>(p.gpart + col4, p.C4, 0, p.ngroups, (int64_t)BN_GROUP * p.chunk, p.T, a, m2);
     const int c = col4 * 4;
     if (BWD) {
         p.sums[col4] = a;
@@ -229,8 +153,8 @@ __global__ __launch_bounds__(BN_THREADS) void batchnorm_finalize_kernel(BnP p) {
 }
 
 // eval mode: the statistics are the running buffers
-__global__ __launch_bounds__(BN_THREADS) void batchnorm_eval_stats_kernel(BnP p) {
-    const int col4 = blockIdx.x * BN_THREADS + threadIdx.x;
+__global__ __launch_bounds__(COL_THREADS) void batchnorm_eval_stats_kernel(BnP p) {
+    const int col4 = blockIdx.x * COL_THREADS + threadIdx.x;
     if (col4 >= p.C4) return;
     const int c = col4 * 4;
     f32x4 mean, rstd;
@@ -245,11 +169,10 @@ __global__ __launch_bounds__(BN_THREADS) void batchnorm_eval_stats_kernel(BnP p)
 }
 
 template <bool BWD>
-__global__ __launch_bounds__(BN_THREADS) void batchnorm_apply_kernel(BnP p) {
-    const int t = threadIdx.x;
-    const int cl = t % p.CG, rl = t / p.CG;
-    const int col4 = blockIdx.y * p.CG + cl;
-    if (!(rl < p.RL && col4 < p.C4)) return;
+__global__ __launch_bounds__(COL_THREADS) void batchnorm_apply_kernel(BnP p) {
+    const ColLane L = col_lane(p.CG, p.RL, p.C4, blockIdx.y);
+    const int col4 = L.col4;
+    if (!L.active) return;
     f32x4 mean, rstd, sc, sh = {0.f, 0.f, 0.f, 0.f};      // sc = rstd gamma ; sh = beta
     bn_load_stats(p, col4, mean, rstd);
 #pragma unroll
@@ -264,13 +187,13 @@ __global__ __launch_bounds__(BN_THREADS) void batchnorm_apply_kernel(BnP p) {
         m2 = p.sums[p.C4 + col4] * inv;
     }
     const uint32_t key = BWD ? drop_key_dev(p.drop) : 0u;
-    const int64_t row0 = blockIdx.x * p.chunk, row1 = min64(p.T, row0 + p.chunk);
+    const ColRows<int64_t> R = col_rows((int)blockIdx.x, p.chunk, p.T);
     const f32x4* X4 = reinterpret_cast<const f32x4*>(p.X) + col4;
     const f32x4* G4 = reinterpret_cast<const f32x4*>(p.G) + col4;
     const f32x4* A4 = reinterpret_cast<const f32x4*>(p.A) + col4;
     f32x4* Y4 = reinterpret_cast<f32x4*>(p.Y) + col4;
 #pragma unroll 4
-    for (int64_t r = row0 + rl; r < row1; r += p.RL) {
+    for (int64_t r = R.r0 + L.rl; r < R.r1; r += p.RL) {
         const f32x4 x = X4[r * p.C4];
         f32x4 y;
         if (BWD) {
@@ -306,14 +229,14 @@ int batchnorm_run(BnP p, void* ws, int64_t ws_bytes, void* stream) {
     p.part = reinterpret_cast<f32x4*>(ws);
     p.gpart = p.part + (int64_t)g.nchunks * 2 * g.C4;
     p.sums = p.gpart + (int64_t)g.ngroups * 2 * g.C4;
-    const dim3 grid((unsigned)g.nchunks, (unsigned)g.ncb), block(BN_THREADS);
-    const dim3 cols((unsigned)((g.C4 + BN_THREADS - 1) / BN_THREADS));
+    const dim3 grid((unsigned)g.nchunks, (unsigned)g.ncb), block(COL_THREADS);
+    const dim3 cols((unsigned)((g.C4 + COL_THREADS - 1) / COL_THREADS));
     hipStream_t st = (hipStream_t)stream;
     if (BWD || p.training) {
         hipLaunchKernelGGL(batchnorm_partial_kernel<BWD>, grid, block, 0, st, p);
         GT_LAUNCH_CHECK();
         hipLaunchKernelGGL(batchnorm_group_kernel<BWD>,
-                           dim3((unsigned)(((int64_t)g.ngroups * g.C4 + BN_THREADS - 1) / BN_THREADS)), block, 0, st, p);
+                           dim3((unsigned)(((int64_t)g.ngroups * g.C4 + COL_THREADS - 1) / COL_THREADS)), block, 0, st, p);
         GT_LAUNCH_CHECK();
         hipLaunchKernelGGL(batchnorm_finalize_kernel<BWD>, cols, block, 0, st, p);
         GT_LAUNCH_CHECK();

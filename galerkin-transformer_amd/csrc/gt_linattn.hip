@@ -12,7 +12,7 @@
 
 #include <algorithm>
 
-#include "gt_common.h"
+#include "gt_colpass.h"
 
 namespace gt {
 namespace {
@@ -154,27 +154,19 @@ __global__ __launch_bounds__(FS_THREADS) void feature_softmax_bwd_kernel(const f
 
 // ------------------------------------------------------------------------------------------ token softmax
 // One batch item is a dense [n][C4] array of float4 (C4 = h * DP / 4 column groups), contiguous along the columns, and the
-// softmax runs down the rows.  A block owns TS_CHUNK consecutive tokens of one batch item and CG <= 256 adjacent column
-// groups; its threads form RL = 256 / CG row lanes, so a wave reads whole contiguous rows.  Pass 1 keeps a running
-// (max, sum) per column and row lane (online rescaling), merges the row lanes in LDS in lane order and writes one partial
-// per (batch, chunk, column).  Pass 2 merges the partials of all chunks -- chunks q = lane, lane + RL, ... per row lane,
-// then the lanes in order, the same order in every block -- and writes exp(x - max) / sum for its own tokens.
+// softmax runs down the rows: the block shape and the lane-order merge are those of gt_colpass.h.  A block owns TS_CHUNK
+// consecutive tokens of one batch item and CG <= 256 adjacent column groups; its threads form RL = 256 / CG row lanes, so a
+// wave reads whole contiguous rows.  Pass 1 keeps a running (max, sum) per column and row lane (online rescaling), merges
+// the row lanes in LDS in lane order and writes one partial per (batch, chunk, column).  Pass 2 merges the partials of all
+// chunks -- chunks q = lane, lane + RL, ... per row lane, then the lanes in order, the same order in every block -- and
+// writes exp(x - max) / sum for its own tokens.
 // The backward is the same pair of passes with plain sums:  c = sum_t K~ .* dK~,  dK' = K~ .* (dK~ - c).
-constexpr int TS_THREADS = 256;
-constexpr int TS_CHUNK = 128;
+constexpr int TS_CHUNK = 128;      // constant, whatever the batch: the chunk count fixes pass 2's merge order
 
-struct TsGeom {
-    int C4, CG, RL, nchunks, ncb;
+struct TsGeom : ColGeom {
+    int nchunks;
 };
-static inline TsGeom ts_geom(int n, int h, int DP) {
-    TsGeom g;
-    g.C4 = h * DP / 4;
-    g.CG = std::min(g.C4, TS_THREADS);
-    g.RL = TS_THREADS / g.CG;
-    g.nchunks = (n + TS_CHUNK - 1) / TS_CHUNK;
-    g.ncb = (g.C4 + g.CG - 1) / g.CG;
-    return g;
-}
+static inline TsGeom ts_geom(int n, int h, int DP) { return {col_geom(h * DP / 4), (n + TS_CHUNK - 1) / TS_CHUNK}; }
 
 // (m, s) <- (m, s) merged with (m2, s2); an empty side has s == 0 (and m == -inf)
 __device__ __forceinline__ void ts_merge(f32x4& m, f32x4& s, const f32x4 m2, const f32x4 s2) {
@@ -195,27 +187,29 @@ struct TsP {
     int n, C4, CG, RL, nchunks, DP, Dr;
 };
 
+// lanes 1 .. RL-1 of column cl folded into (m, s) in lane order; the backward has sums only and never reads the max array
 template <bool BWD>
-__global__ __launch_bounds__(TS_THREADS) void token_softmax_stats_kernel(TsP p) {
-    __shared__ f32x4 sm[TS_THREADS], ss[TS_THREADS];
+__device__ __forceinline__ void ts_fold_lanes(const f32x4* sm, const f32x4* ss, const TsP& p, int cl, f32x4& m, f32x4& s) {
+    col_fold_lanes(sm, ss, p.CG, p.RL, cl, [&](const f32x4 m2, const f32x4 s2, int) {
+        if (BWD) s += s2;
+        else ts_merge(m, s, m2, s2);
+    });
+}
+
+template <bool BWD>
+__global__ __launch_bounds__(COL_THREADS) void token_softmax_stats_kernel(TsP p) {
+    __shared__ f32x4 sm[COL_THREADS], ss[COL_THREADS];
     const int t = threadIdx.x;
-    const int cl = t % p.CG, rl = t / p.CG;
-    const int col4 = blockIdx.z * p.CG + cl;
-    const int b = blockIdx.y, chunk = blockIdx.x;
-    const bool active = rl < p.RL && col4 < p.C4;
-    const int row0 = chunk * TS_CHUNK, row1 = min(p.n, row0 + TS_CHUNK);
-    f32x4 m, s;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        m[j] = -INFINITY;
-        s[j] = 0.f;
-    }
-    if (active) {
+    const ColLane L = col_lane(p.CG, p.RL, p.C4, blockIdx.z);
+    const int b = blockIdx.y, chunk = blockIdx.x, col4 = L.col4;
+    const ColRows<int> R = col_rows(chunk, TS_CHUNK, p.n);
+    f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, s = {0.f, 0.f, 0.f, 0.f};      // the empty partial
+    if (L.active) {
         const int64_t base = (int64_t)b * p.n * p.C4 + col4;
         const f32x4* X4 = reinterpret_cast<const f32x4*>(p.X) + base;
         const f32x4* G4 = reinterpret_cast<const f32x4*>(p.G) + base;
 #pragma unroll 4
-        for (int r = row0 + rl; r < row1; r += p.RL) {
+        for (int r = R.r0 + L.rl; r < R.r1; r += p.RL) {
             const f32x4 x = X4[(int64_t)r * p.C4];
             if (BWD) {
                 s += x * G4[(int64_t)r * p.C4];
@@ -236,12 +230,8 @@ __global__ __launch_bounds__(TS_THREADS) void token_softmax_stats_kernel(TsP p) 
     sm[t] = m;
     ss[t] = s;
     __syncthreads();
-    if (active && rl == 0) {
-        for (int q = 1; q < p.RL; ++q) {
-            const f32x4 m2 = sm[q * p.CG + cl], s2 = ss[q * p.CG + cl];
-            if (BWD) s += s2;
-            else ts_merge(m, s, m2, s2);
-        }
+    if (L.active && L.rl == 0) {
+        ts_fold_lanes<BWD>(sm, ss, p, L.cl, m, s);
         if (BWD) {
             p.part[((int64_t)b * p.nchunks + chunk) * p.C4 + col4] = s;
         } else {
@@ -253,21 +243,14 @@ __global__ __launch_bounds__(TS_THREADS) void token_softmax_stats_kernel(TsP p) 
 }
 
 template <bool BWD>
-__global__ __launch_bounds__(TS_THREADS) void token_softmax_apply_kernel(TsP p) {
-    __shared__ f32x4 sm[TS_THREADS], ss[TS_THREADS];
+__global__ __launch_bounds__(COL_THREADS) void token_softmax_apply_kernel(TsP p) {
+    __shared__ f32x4 sm[COL_THREADS], ss[COL_THREADS];
     const int t = threadIdx.x;
-    const int cl = t % p.CG, rl = t / p.CG;
-    const int col4 = blockIdx.z * p.CG + cl;
-    const int b = blockIdx.y, chunk = blockIdx.x;
-    const bool active = rl < p.RL && col4 < p.C4;
-    f32x4 m, s;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        m[j] = -INFINITY;
-        s[j] = 0.f;
-    }
-    if (active) {
-        for (int q = rl; q < p.nchunks; q += p.RL) {
+    const ColLane L = col_lane(p.CG, p.RL, p.C4, blockIdx.z);
+    const int b = blockIdx.y, chunk = blockIdx.x, col4 = L.col4;
+    f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, s = {0.f, 0.f, 0.f, 0.f};      // the empty partial
+    if (L.active) {
+        for (int q = L.rl; q < p.nchunks; q += p.RL) {
             if (BWD) {
                 s += p.part[((int64_t)b * p.nchunks + q) * p.C4 + col4];
             } else {
@@ -280,14 +263,10 @@ __global__ __launch_bounds__(TS_THREADS) void token_softmax_apply_kernel(TsP p) 
     sm[t] = m;
     ss[t] = s;
     __syncthreads();
-    if (!active) return;
-    m = sm[cl];
-    s = ss[cl];
-    for (int q = 1; q < p.RL; ++q) {
-        const f32x4 m2 = sm[q * p.CG + cl], s2 = ss[q * p.CG + cl];
-        if (BWD) s += s2;
-        else ts_merge(m, s, m2, s2);
-    }
+    if (!L.active) return;
+    m = sm[L.cl];
+    s = ss[L.cl];
+    ts_fold_lanes<BWD>(sm, ss, p, L.cl, m, s);
     bool valid[4];
     const int c0 = (col4 * 4) % p.DP;        // DP % 4 == 0: a float4 never straddles two heads
 #pragma unroll
@@ -295,13 +274,13 @@ __global__ __launch_bounds__(TS_THREADS) void token_softmax_apply_kernel(TsP p) 
         valid[j] = c0 + j < p.Dr;
         if (!BWD) s[j] = 1.f / s[j];
     }
-    const int row0 = chunk * TS_CHUNK, row1 = min(p.n, row0 + TS_CHUNK);
+    const ColRows<int> R = col_rows(chunk, TS_CHUNK, p.n);
     const int64_t base = (int64_t)b * p.n * p.C4 + col4;
     const f32x4* X4 = reinterpret_cast<const f32x4*>(p.X) + base;
     const f32x4* G4 = reinterpret_cast<const f32x4*>(p.G) + base;
     f32x4* Y4 = reinterpret_cast<f32x4*>(p.Y) + base;
 #pragma unroll 4
-    for (int r = row0 + rl; r < row1; r += p.RL) {
+    for (int r = R.r0 + L.rl; r < R.r1; r += p.RL) {
         const f32x4 x = X4[(int64_t)r * p.C4];
         f32x4 y;
         if (BWD) {
@@ -316,26 +295,22 @@ __global__ __launch_bounds__(TS_THREADS) void token_softmax_apply_kernel(TsP p) 
     }
 }
 
-static inline bool linattn_shape_ok(int dk, int p) {
-    return (dk == 16 || dk == 32 || dk == 48 || dk == 64 || dk == 96) && p >= 0 && p <= 2;
-}
-
 template <bool BWD>
 int token_softmax_run(const float* X, const float* G, float* Y, int B, int n, int h, int dk, int pd, void* ws,
                       int64_t ws_bytes, void* stream) {
     if (!X || !Y || (BWD && !G) || B <= 0 || n <= 0 || h <= 0) return GT_EINVAL;
-    if (!linattn_shape_ok(dk, pd) || B > 65535) return GT_ENOTSUP;
+    if (!head_tile_shape_ok(dk, pd) || B > 65535) return GT_ENOTSUP;
     if (misaligned16(X, G, Y, ws)) return GT_EALIGN;
     if (!ws || ws_bytes < gt_token_softmax_ws_bytes(B, n, h, dk, pd)) return GT_EWS;
-    const int Dr = dk + pd, DP = (Dr + 3) & ~3;
+    const int Dr = dk + pd, DP = round4(Dr);
     const TsGeom g = ts_geom(n, h, DP);
     if (g.ncb > 65535) return GT_ENOTSUP;
     TsP p{X, G, Y, reinterpret_cast<f32x4*>(ws), n, g.C4, g.CG, g.RL, g.nchunks, DP, Dr};
     dim3 grid((unsigned)g.nchunks, (unsigned)B, (unsigned)g.ncb);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(token_softmax_stats_kernel<BWD>, grid, dim3(TS_THREADS), 0, st, p);
+    hipLaunchKernelGGL(token_softmax_stats_kernel<BWD>, grid, dim3(COL_THREADS), 0, st, p);
     GT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(token_softmax_apply_kernel<BWD>, grid, dim3(TS_THREADS), 0, st, p);
+    hipLaunchKernelGGL(token_softmax_apply_kernel<BWD>, grid, dim3(COL_THREADS), 0, st, p);
     GT_LAUNCH_CHECK();
     return 0;
 }
@@ -347,9 +322,9 @@ using namespace gt;
 
 extern "C" int gt_feature_softmax_fwd(const float* X, float* Y, int64_t rows, int32_t dk, int32_t p, void* stream) {
     if (!X || !Y || rows <= 0) return GT_EINVAL;
-    if (!linattn_shape_ok(dk, p)) return GT_ENOTSUP;
+    if (!head_tile_shape_ok(dk, p)) return GT_ENOTSUP;
     if (misaligned16(X, Y)) return GT_EALIGN;
-    const int Dr = dk + p, L4 = ((Dr + 3) & ~3) / 4, S = fs_segments(L4);
+    const int Dr = dk + p, L4 = round4(Dr) / 4, S = fs_segments(L4);
     const int64_t nblk = (rows + S - 1) / S;
     if (nblk > 0x7fffffff) return GT_ENOTSUP;
     hipLaunchKernelGGL(feature_softmax_fwd_kernel, dim3((unsigned)nblk), dim3(FS_THREADS), 0, (hipStream_t)stream, X, Y, rows,
@@ -361,9 +336,9 @@ extern "C" int gt_feature_softmax_fwd(const float* X, float* Y, int64_t rows, in
 extern "C" int gt_feature_softmax_bwd(const float* Y, const float* dY, float* dX, int64_t rows, int32_t dk, int32_t p,
                                       void* stream) {
     if (!Y || !dY || !dX || rows <= 0) return GT_EINVAL;
-    if (!linattn_shape_ok(dk, p)) return GT_ENOTSUP;
+    if (!head_tile_shape_ok(dk, p)) return GT_ENOTSUP;
     if (misaligned16(Y, dY, dX)) return GT_EALIGN;
-    const int Dr = dk + p, L4 = ((Dr + 3) & ~3) / 4, S = fs_segments(L4);
+    const int Dr = dk + p, L4 = round4(Dr) / 4, S = fs_segments(L4);
     const int64_t nblk = (rows + S - 1) / S;
     if (nblk > 0x7fffffff) return GT_ENOTSUP;
     hipLaunchKernelGGL(feature_softmax_bwd_kernel, dim3((unsigned)nblk), dim3(FS_THREADS), 0, (hipStream_t)stream, Y, dY, dX,
@@ -373,8 +348,8 @@ extern "C" int gt_feature_softmax_bwd(const float* Y, const float* dY, float* dX
 }
 
 extern "C" int64_t gt_token_softmax_ws_bytes(int32_t B, int32_t n, int32_t h, int32_t dk, int32_t p) {
-    if (B <= 0 || n <= 0 || h <= 0 || !linattn_shape_ok(dk, p)) return 0;
-    const TsGeom g = ts_geom(n, h, (dk + p + 3) & ~3);
+    if (B <= 0 || n <= 0 || h <= 0 || !head_tile_shape_ok(dk, p)) return 0;
+    const TsGeom g = ts_geom(n, h, round4(dk + p));
     return (int64_t)B * g.nchunks * 2 * g.C4 * (int64_t)sizeof(f32x4);
 }
 

@@ -5,46 +5,31 @@
 // on the head-tile layout [B*n][h][DP], DP = round4(dk + p), fp32.  The p coordinate columns pass through unchanged and the
 // pad columns dk + p .. DP-1 are written as exact zeros (forward and backward).
 //
-// One batch item is a dense [n][C4] array of float4 (C4 = h * DP / 4), as in the token softmax (gt_linattn.hip), and the
-// passes have its shape: a block owns `chunk` consecutive tokens of one sample and CG <= 256 adjacent column groups, its
-// threads form RL = 256 / CG row lanes.
-//     forward : partial   per (sample, chunk, column): Welford (mean, M2) per row lane, lanes merged in lane order; the
-//                         values are taken relative to the column's first token of the sample (a pivot common to all
-//                         partials), so a large common offset costs the running means no digits
-//               finalize  per (sample, column): the chunks merged in chunk order (Chan's pairwise update), pivot added
-//                         back once -> stats
+// One batch item is a dense [n][C4] array of float4 (C4 = h * DP / 4) and the passes are the column-statistics passes of
+// gt_colpass.h, which states the block shape, the Welford / pivot / Chan arithmetic and the merge orders: a block owns `chunk`
+// consecutive tokens of one sample and CG <= 256 adjacent column groups, its threads form RL = 256 / CG row lanes.
+//     forward : partial   per (sample, chunk, column): (mean, M2) relative to the column's first token of the sample
+//               finalize  per (sample, column): the chunks merged in chunk order, pivot added back once -> stats
 //               apply     y = (x - mean) * (rstd gamma) + beta
 //     backward: partial   s1 = sum dY, s2 = sum dY xh per (sample, chunk, column), xh recomputed from x and stats
 //               finalize  chunks summed in order per (sample, column)
 //               apply     dX = rstd gamma (dY - s1/n - xh s2/n)
 //               params    dgamma = sum_b s2, dbeta = sum_b s1, samples in order
-// The variance is never formed as E[x^2] - mean^2: a column with |mean| >> std keeps its digits.  No atomics, every merge
-// in a fixed order: two runs give the same bits.  In place is allowed (Y == X, dX == dY): the statistics are complete
-// before the applying launch starts, and there every thread reads the elements it owns before it writes them.
+// In place is allowed (Y == X, dX == dY): the statistics are complete before the applying launch starts, and there every
+// thread reads the elements it owns before it writes them.
 #include <math.h>
 
-#include <algorithm>
-
-#include "gt_common.h"
+#include "gt_colpass.h"
 
 namespace gt {
 namespace {
 
-constexpr int TN_THREADS = 256;
-constexpr int TN_CHUNK_MAX = 128, TN_CHUNK_MIN = 32;
-constexpr int TN_MIN_BLOCKS = 1024;      // four blocks per CU of the 256 before the chunks stop shrinking
-
-struct TnGeom {
-    int C4, CG, RL, chunk, nchunks, ncb;
+struct TnGeom : ColGeom {
+    int chunk, nchunks;
 };
 static inline TnGeom tn_geom(int B, int n, int h, int DP) {
-    TnGeom g;
-    g.C4 = h * DP / 4;
-    g.CG = std::min(g.C4, TN_THREADS);
-    g.RL = TN_THREADS / g.CG;
-    g.ncb = (g.C4 + g.CG - 1) / g.CG;
-    g.chunk = TN_CHUNK_MAX;      // small batches: shorter chunks, so that B * nchunks blocks still cover the device
-    while (g.chunk > TN_CHUNK_MIN && (int64_t)B * ((n + g.chunk - 1) / g.chunk) * g.ncb < TN_MIN_BLOCKS) g.chunk >>= 1;
+    TnGeom g{col_geom(h * DP / 4), 0, 0};
+    g.chunk = col_chunk(n, (int64_t)B * g.ncb);      // small batches: shorter chunks
     g.nchunks = (n + g.chunk - 1) / g.chunk;
     return g;
 }
@@ -63,16 +48,6 @@ struct TnP {
     int n, h, dk, pd, DP, C4, CG, RL, chunk, nchunks;
     float eps;
 };
-
-// (mean, M2, na) <- merged with (mb, Mb, nb): Chan et al.'s pairwise update.  na == 0 gives (mb, Mb) exactly.
-__device__ __forceinline__ void tn_merge(f32x4& mean, f32x4& M2, float& na, const f32x4 mb, const f32x4 Mb, const float nb) {
-    if (nb == 0.f) return;
-    const float nt = na + nb, w = nb / nt;
-    const f32x4 d = mb - mean;
-    mean += d * w;
-    M2 += Mb + d * d * (na * w);
-    na = nt;
-}
 
 // value channel of component j of column group col4 (or -1: coordinate / pad column), and the head
 __device__ __forceinline__ void tn_columns(const TnP& p, int col4, int& head, int ch[4], bool coord[4]) {
@@ -101,60 +76,29 @@ __device__ __forceinline__ void tn_load_stats(const TnP& p, int b, int head, con
 }
 
 template <bool BWD>
-__global__ __launch_bounds__(TN_THREADS) void token_norm_partial_kernel(TnP p) {
-    __shared__ f32x4 sa[TN_THREADS], sb[TN_THREADS];
-    const int t = threadIdx.x;
-    const int cl = t % p.CG, rl = t / p.CG;
-    const int col4 = blockIdx.z * p.CG + cl;
+__global__ __launch_bounds__(COL_THREADS) void token_norm_partial_kernel(TnP p) {
+    __shared__ f32x4 sa[COL_THREADS], sb[COL_THREADS];
+    const ColLane L = col_lane(p.CG, p.RL, p.C4, blockIdx.z);
     const int b = blockIdx.y, chunk = blockIdx.x;
-    const bool active = rl < p.RL && col4 < p.C4;
-    const int row0 = chunk * p.chunk, row1 = min(p.n, row0 + p.chunk);
+    const ColRows<int> R = col_rows(chunk, p.chunk, p.n);
     f32x4 a = {0.f, 0.f, 0.f, 0.f}, m2 = {0.f, 0.f, 0.f, 0.f};      // fwd: (mean, M2) ; bwd: (s1, s2)
-    if (active) {
-        const int64_t base = (int64_t)b * p.n * p.C4 + col4;
+    if (L.active) {
+        const int64_t base = (int64_t)b * p.n * p.C4 + L.col4;      // the sample's first token: the pivot row
         const f32x4* X4 = reinterpret_cast<const f32x4*>(p.X) + base;
         if (BWD) {
-            const f32x4* G4 = reinterpret_cast<const f32x4*>(p.G) + base;
             int head, ch[4];
             bool coord[4];
             f32x4 mean, rstd;
-            tn_columns(p, col4, head, ch, coord);
+            tn_columns(p, L.col4, head, ch, coord);
             tn_load_stats(p, b, head, ch, mean, rstd);
-#pragma unroll 4
-            for (int r = row0 + rl; r < row1; r += p.RL) {
-                const f32x4 x = X4[(int64_t)r * p.C4], g = G4[(int64_t)r * p.C4];
-                a += g;
-                m2 += g * ((x - mean) * rstd);
-            }
+            col_gsum_rows(X4, reinterpret_cast<const f32x4*>(p.G) + base, p.C4, R.r0 + L.rl, R.r1, p.RL, mean, rstd, a, m2);
         } else {
-            const f32x4 piv = X4[0];      // the sample's first token: every partial of a column is taken relative to it
-            float cnt = 0.f;
-#pragma unroll 4
-            for (int r = row0 + rl; r < row1; r += p.RL) {
-                const f32x4 x = X4[(int64_t)r * p.C4] - piv;
-                cnt += 1.f;
-                const f32x4 d = x - a;
-                a += d * (1.f / cnt);
-                m2 += d * (x - a);
-            }
+            col_welford_rows(X4, p.C4, R.r0 + L.rl, R.r1, p.RL, a, m2);
         }
     }
-    sa[t] = a;
-    sb[t] = m2;
-    __syncthreads();
-    if (active && rl == 0) {
-        const int rows = row1 - row0;
-        float na = (float)((rows + p.RL - 1) / p.RL);      // rows of lane 0; lane q has (rows - q + RL - 1) / RL
-        for (int q = 1; q < p.RL; ++q) {
-            const f32x4 a2 = sa[q * p.CG + cl], b2 = sb[q * p.CG + cl];
-            if (BWD) {
-                a += a2;
-                m2 += b2;
-            } else {
-                tn_merge(a, m2, na, a2, b2, q < rows ? (float)((rows - q + p.RL - 1) / p.RL) : 0.f);
-            }
-        }
-        f32x4* o = p.part + ((int64_t)b * p.nchunks + chunk) * 2 * p.C4 + col4;
+    col_merge_lanes<BWD>(sa, sb, L, p.CG, p.RL, R.r1 - R.r0, a, m2);
+    if (L.active && L.rl == 0) {
+        f32x4* o = p.part + ((int64_t)b * p.nchunks + chunk) * 2 * p.C4 + L.col4;
         o[0] = a;
         o[p.C4] = m2;
     }
@@ -162,22 +106,13 @@ __global__ __launch_bounds__(TN_THREADS) void token_norm_partial_kernel(TnP p) {
 
 // one thread per (sample, column group): the chunk partials in chunk order
 template <bool BWD>
-__global__ __launch_bounds__(TN_THREADS) void token_norm_finalize_kernel(TnP p, int B) {
-    const int64_t idx = (int64_t)blockIdx.x * TN_THREADS + threadIdx.x;
+__global__ __launch_bounds__(COL_THREADS) void token_norm_finalize_kernel(TnP p, int B) {
+    const int64_t idx = (int64_t)blockIdx.x * COL_THREADS + threadIdx.x;
     if (idx >= (int64_t)B * p.C4) return;
     const int b = (int)(idx / p.C4), col4 = (int)(idx - (int64_t)b * p.C4);
     const f32x4* o = p.part + (int64_t)b * p.nchunks * 2 * p.C4 + col4;
     f32x4 a = {0.f, 0.f, 0.f, 0.f}, m2 = {0.f, 0.f, 0.f, 0.f};
-    float na = 0.f;
-    for (int q = 0; q < p.nchunks; ++q) {
-        const f32x4 a2 = o[(int64_t)q * 2 * p.C4], b2 = o[(int64_t)q * 2 * p.C4 + p.C4];
-        if (BWD) {
-            a += a2;
-            m2 += b2;
-        } else {
-            tn_merge(a, m2, na, a2, b2, (float)(min(p.n, (q + 1) * p.chunk) - q * p.chunk));
-        }
-    }
+    col_merge_chunks<BWD>(o, p.C4, 0, p.nchunks, p.chunk, p.n, a, m2);
     if (BWD) {
         p.sums[((int64_t)b * 2 + 0) * p.C4 + col4] = a;
         p.sums[((int64_t)b * 2 + 1) * p.C4 + col4] = m2;
@@ -198,12 +133,10 @@ __global__ __launch_bounds__(TN_THREADS) void token_norm_finalize_kernel(TnP p, 
 }
 
 template <bool BWD>
-__global__ __launch_bounds__(TN_THREADS) void token_norm_apply_kernel(TnP p) {
-    const int t = threadIdx.x;
-    const int cl = t % p.CG, rl = t / p.CG;
-    const int col4 = blockIdx.z * p.CG + cl;
-    const int b = blockIdx.y, chunk = blockIdx.x;
-    if (!(rl < p.RL && col4 < p.C4)) return;
+__global__ __launch_bounds__(COL_THREADS) void token_norm_apply_kernel(TnP p) {
+    const ColLane L = col_lane(p.CG, p.RL, p.C4, blockIdx.z);
+    const int b = blockIdx.y, col4 = L.col4;
+    if (!L.active) return;
     int head, ch[4];
     bool coord[4];
     f32x4 mean, rstd, sc, sh = {0.f, 0.f, 0.f, 0.f};      // sc = rstd gamma ; sh = beta
@@ -220,13 +153,13 @@ __global__ __launch_bounds__(TN_THREADS) void token_norm_apply_kernel(TnP p) {
         m1 = p.sums[((int64_t)b * 2 + 0) * p.C4 + col4] * inv;
         m2 = p.sums[((int64_t)b * 2 + 1) * p.C4 + col4] * inv;
     }
-    const int row0 = chunk * p.chunk, row1 = min(p.n, row0 + p.chunk);
+    const ColRows<int> R = col_rows((int)blockIdx.x, p.chunk, p.n);
     const int64_t base = (int64_t)b * p.n * p.C4 + col4;
     const f32x4* X4 = reinterpret_cast<const f32x4*>(p.X) + base;
     const f32x4* G4 = reinterpret_cast<const f32x4*>(p.G) + base;
     f32x4* Y4 = reinterpret_cast<f32x4*>(p.Y) + base;
 #pragma unroll 4
-    for (int r = row0 + rl; r < row1; r += p.RL) {
+    for (int r = R.r0 + L.rl; r < R.r1; r += p.RL) {
         const f32x4 x = X4[(int64_t)r * p.C4];
         f32x4 y;
         if (BWD) {
@@ -243,8 +176,8 @@ __global__ __launch_bounds__(TN_THREADS) void token_norm_apply_kernel(TnP p) {
 }
 
 // dgamma = sum_b s2, dbeta = sum_b s1: one thread per column group, samples in order
-__global__ __launch_bounds__(TN_THREADS) void token_norm_params_kernel(TnP p, int B) {
-    const int col4 = blockIdx.x * TN_THREADS + threadIdx.x;
+__global__ __launch_bounds__(COL_THREADS) void token_norm_params_kernel(TnP p, int B) {
+    const int col4 = blockIdx.x * COL_THREADS + threadIdx.x;
     if (col4 >= p.C4) return;
     f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
     for (int b = 0; b < B; ++b) {
@@ -262,40 +195,32 @@ __global__ __launch_bounds__(TN_THREADS) void token_norm_params_kernel(TnP p, in
         }
 }
 
-static inline bool tn_shape_ok(int dk, int p) {      // the head sizes of the softmax pair (gt_linattn.hip)
-    return (dk == 16 || dk == 32 || dk == 48 || dk == 64 || dk == 96) && p >= 0 && p <= 2;
-}
-static inline bool tn_misaligned(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
-    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-             reinterpret_cast<uintptr_t>(d)) & 15) != 0;
-}
-
 template <bool BWD>
 int token_norm_run(const float* X, const float* G, const float* gamma, const float* beta, float eps, float* Y, float* stats,
                    float* dgamma, float* dbeta, int B, int n, int h, int dk, int pd, void* ws, int64_t ws_bytes,
                    void* stream) {
     if (!X || !Y || !gamma || !stats || (BWD ? !G : !beta) || B <= 0 || n <= 0 || h <= 0) return GT_EINVAL;
     if (!BWD && !(eps >= 0.f)) return GT_EINVAL;
-    if (!tn_shape_ok(dk, pd) || B > 65535) return GT_ENOTSUP;
-    if (tn_misaligned(X, G, Y, ws) || (reinterpret_cast<uintptr_t>(stats) & 7)) return GT_EALIGN;
+    if (!head_tile_shape_ok(dk, pd) || B > 65535) return GT_ENOTSUP;
+    if (misaligned16(X, G, Y, ws) || (reinterpret_cast<uintptr_t>(stats) & 7)) return GT_EALIGN;
     if (!ws || ws_bytes < gt_token_norm_ws_bytes(B, n, h, dk, pd)) return GT_EWS;
-    const int DP = (dk + pd + 3) & ~3;
+    const int DP = round4(dk + pd);
     const TnGeom g = tn_geom(B, n, h, DP);
     if (g.ncb > 65535) return GT_ENOTSUP;
     f32x4* part = reinterpret_cast<f32x4*>(ws);
     TnP p{X, G, Y, gamma, beta, stats, part, part + (int64_t)B * g.nchunks * 2 * g.C4, dgamma, dbeta,
           n, h, dk, pd, DP, g.C4, g.CG, g.RL, g.chunk, g.nchunks, eps};
     const dim3 grid((unsigned)g.nchunks, (unsigned)B, (unsigned)g.ncb);
-    const dim3 flat((unsigned)(((int64_t)B * g.C4 + TN_THREADS - 1) / TN_THREADS));
+    const dim3 flat((unsigned)(((int64_t)B * g.C4 + COL_THREADS - 1) / COL_THREADS));
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(token_norm_partial_kernel<BWD>, grid, dim3(TN_THREADS), 0, st, p);
+    hipLaunchKernelGGL(token_norm_partial_kernel<BWD>, grid, dim3(COL_THREADS), 0, st, p);
     GT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(token_norm_finalize_kernel<BWD>, flat, dim3(TN_THREADS), 0, st, p, B);
+    hipLaunchKernelGGL(token_norm_finalize_kernel<BWD>, flat, dim3(COL_THREADS), 0, st, p, B);
     GT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(token_norm_apply_kernel<BWD>, grid, dim3(TN_THREADS), 0, st, p);
+    hipLaunchKernelGGL(token_norm_apply_kernel<BWD>, grid, dim3(COL_THREADS), 0, st, p);
     GT_LAUNCH_CHECK();
     if (BWD && (dgamma || dbeta)) {
-        hipLaunchKernelGGL(token_norm_params_kernel, dim3((unsigned)((g.C4 + TN_THREADS - 1) / TN_THREADS)), dim3(TN_THREADS),
+        hipLaunchKernelGGL(token_norm_params_kernel, dim3((unsigned)((g.C4 + COL_THREADS - 1) / COL_THREADS)), dim3(COL_THREADS),
                            0, st, p, B);
         GT_LAUNCH_CHECK();
     }
@@ -308,8 +233,8 @@ int token_norm_run(const float* X, const float* G, const float* gamma, const flo
 using namespace gt;
 
 extern "C" int64_t gt_token_norm_ws_bytes(int32_t B, int32_t n, int32_t h, int32_t dk, int32_t p) {
-    if (B <= 0 || n <= 0 || h <= 0 || !tn_shape_ok(dk, p)) return 0;
-    const TnGeom g = tn_geom(B, n, h, (dk + p + 3) & ~3);
+    if (B <= 0 || n <= 0 || h <= 0 || !head_tile_shape_ok(dk, p)) return 0;
+    const TnGeom g = tn_geom(B, n, h, round4(dk + p));
     return ((int64_t)B * g.nchunks + B) * 2 * g.C4 * (int64_t)sizeof(f32x4);
 }
 

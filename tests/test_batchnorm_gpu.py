@@ -28,7 +28,10 @@ from test_modules_gpu import build_module, run_module
 pytestmark = pytest.mark.gpu
 
 KTOL = 2e-6
-WIDTHS = (32, 96, 192, 256, 384)
+WIDTHS = (32, 96, 192, 256, 384, 1200)
+# f = 1200 is 300 column groups: a single row lane (RL = 1) and two column blocks, the second with 44 live lanes of 256; the
+# other widths have one column block and RL >= 2.  It is about the columns, so it runs at one row count.
+WIDE, WIDE_ROWS = 1200, (150,)
 # no multiple of a chunk length (32 .. 128 rows); 2 * 141^2 rows make 1243 chunks, i.e. 20 groups for the second merge level
 ROWS = (33, 150, 1849, 2 * 141 * 141)
 MODES = (None, "f32", "bf16")          # None: the default arithmetic
@@ -146,7 +149,7 @@ def _kernel_errors(_hip, x, dz, gamma, beta, rm, rv, eps, momentum, training, se
 def test_batchnorm_kernels(GT, gpu_device, f, training):
     from galerkin_transformer import _hip
     eps, momentum = 1e-5, 0.1
-    for T in ROWS:
+    for T in (WIDE_ROWS if f == WIDE else ROWS):
         data = _data(T, f, gpu_device, 1000 * f + T)
         errs = _kernel_errors(_hip, *data, eps, momentum, training, seed=f + T)
         print(f, T, "train" if training else "eval", {k: f"{v:.1e}" for k, v in errs.items()})

@@ -35,6 +35,9 @@ HEADS = ((16, 1), (32, 2), (48, 2), (64, 0), (96, 2))
 # 33, 150, 1849: no multiple of any chunk length.  (Not n = 2: there xh = +-1 whatever the data, so dX vanishes in exact
 # arithmetic up to eps and a relative error of it measures nothing; the operator test below runs n = 8.)
 NS = (33, 150, 1849)
+# (B, h, n) run once more at (dk, p) = (96, 2): C4 = 12 * 100 / 4 = 300 column groups, i.e. a single row lane (RL = 1) and two
+# column blocks, the second with 44 live lanes of 256.  Every other shape here has one column block and RL >= 2.
+WIDE = (2, 12, 150)
 
 
 @pytest.fixture(scope="module")
@@ -73,8 +76,8 @@ def _ref64(x, dy, gamma, beta, eps, B, n, h, dk, p):
 @pytest.mark.parametrize("dk,p", HEADS)
 def test_token_norm_kernels(GT, gpu_device, dk, p):
     from galerkin_transformer import _hip
-    B, h, eps = 3, 3, 1e-5
-    for n in NS:
+    eps = 1e-5
+    for B, h, n in [(3, 3, n) for n in NS] + ([WIDE] if (dk, p) == (96, 2) else []):
         x, Dr, DP = _tiles(B, n, h, dk, p, gpu_device, 3000 * dk + 10 * p + n)
         dy = torch.randn_like(x)
         gamma = 1.0 + 0.5 * torch.randn(h, dk, device=gpu_device)
@@ -90,8 +93,8 @@ def test_token_norm_kernels(GT, gpu_device, dk, p):
                     # the mean in units of the column's standard deviation, which is how it enters y (the mean of n unit
                     # normals is ~ n^-1/2: an error relative to itself would measure the data's cancellation)
                     mean=float(((stats[..., 0].double() - mu64) * rstd64).norm() / rstd64.numel() ** 0.5))
-        print(dk, p, n, {k: f"{v:.1e}" for k, v in errs.items()})
-        assert all(v < KTOL for v in errs.values()), (n, errs)
+        print(dk, p, (B, h, n), {k: f"{v:.1e}" for k, v in errs.items()})
+        assert all(v < KTOL for v in errs.values()), ((B, h, n), errs)
         # coordinates pass through untouched, pad columns are exact zeros
         assert torch.equal(yv[..., :p], xv[..., :p]) and torch.equal(dxv[..., :p], dyv[..., :p])
         assert (yv[..., Dr:] == 0).all() and (dxv[..., Dr:] == 0).all()

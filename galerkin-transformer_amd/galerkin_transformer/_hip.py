@@ -179,6 +179,7 @@ _PROTOS = {
     "gt_modemix_fwd": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_int64, C.c_int64] +
                        [C.c_int32] * 3 + [C.c_void_p, C.c_void_p]),
     "gt_modemix_bwd_ws_bytes": (C.c_int64, [C.c_int32] * 4),
+    "gt_modemix_plan": (C.c_int, [C.c_int32] * 4 + [C.POINTER(C.c_int32)] * 3),
     "gt_modemix_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_int64, C.c_int64] +
                        [C.c_int32] * 3 + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
     "gt_bilinear2d_fwd": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 9 + [C.c_void_p]),
@@ -1027,6 +1028,17 @@ def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, stats:
     ws = workspace(x.device, lib().gt_layernorm_bwd_ws_bytes(T, d))
     _launch("gt_layernorm_bwd", dy, x, gamma, stats, T, d, dx, dg, db, ws=ws)
     return dx, dg, db
+
+
+MODEMIX_RESIDENT, MODEMIX_TILED = 0, 1
+
+
+def modemix_plan(B: int, Q: int, Cin: int, Cout: int) -> Tuple[int, int, int]:
+    """(forward route, backward route, batch slices of the backward) the library picks for this shape: MODEMIX_RESIDENT
+    or MODEMIX_TILED per direction (include/gt_hip.h).  Host only: needs no device."""
+    fwd, bwd, slices = C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib().gt_modemix_plan(B, Q, Cin, Cout, C.byref(fwd), C.byref(bwd), C.byref(slices)), "gt_modemix_plan")
+    return fwd.value, bwd.value, slices.value
 
 
 def modemix_fwd(X: torch.Tensor, W: torch.Tensor, Y: torch.Tensor, B: int, Q: int, Cin: int, Cout: int,

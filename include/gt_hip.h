@@ -649,9 +649,23 @@ int64_t gt_layernorm_bwd_ws_bytes(int32_t T, int32_t d);
  * W layout:    [Cin][Cout][Q][2]  (the reference's parameter layout; for 2-D the two corner
  *              blocks are passed as two calls or as Q = modes*modes each via `w_qstride`).
  * Backward: dX from dY and W ;  dW from X and dY (summed over the batch).
- * The batch is cut into slices so that Q x slices blocks fill the chip; the backward's dW partials (one per slice) go
- * through ws (gt_modemix_bwd_ws_bytes, 0 when one slice suffices) and are summed in a fixed order.
+ * Any positive B, Q, Cin, Cout runs.  Two routes, picked per direction by gt_modemix_plan (host only, touches no device;
+ * the two launchers and the workspace query all ask it, so they cannot disagree):
+ *   GT_MODEMIX_RESIDENT  the whole [Cin][Cout] slice of a mode in LDS, one block per (mode, batch slice).
+ *                        Forward: where (2 Cin Cout + 16 Cin) * 4 bytes <= 160 KiB.  Backward: where Cin * Cout <= 6144
+ *                        and (2 Cin (Cout + 1) + 16 Cin + 16 Cout) * 4 bytes <= 160 KiB.
+ *   GT_MODEMIX_TILED     everywhere else: a block owns 4 adjacent modes and a 32-channel output tile (weight gradient: a
+ *                        32 x 32 channel tile), the contraction goes through LDS in chunks; LDS and registers do not
+ *                        depend on the widths.  fp32 FMA chains, no atomics.
+ * Workspace: the backward's dW is summed over `bwd_slices` batch slices; the per-slice partials go through ws
+ * (gt_modemix_bwd_ws_bytes = bwd_slices * Cin * Cout * Q * 2 * 4, or 0 when bwd_slices == 1) and are summed in a fixed order.
+ * Resident: slices = min(ceil(768 / Q), ceil(B / 8)).  Tiled: 1 once (mode groups x channel tiles) fill the chip (>= 256
+ * blocks), else min(ceil(512 / blocks), ceil(B / 8)).
  * ------------------------------------------------------------------------------------------- */
+enum { GT_MODEMIX_RESIDENT = 0, GT_MODEMIX_TILED = 1 };
+/* ABI v21 (additive): the route of each direction and the batch slices of the backward; any out pointer may be NULL. */
+int gt_modemix_plan(int32_t B, int32_t Q, int32_t Cin, int32_t Cout, int32_t* fwd_route, int32_t* bwd_route,
+                    int32_t* bwd_slices);
 int gt_modemix_fwd(const float* X, const float* W, int32_t B, int32_t Q, int32_t Cin, int32_t Cout,
                    int64_t x_bstride, int64_t y_bstride, int32_t q_total_x, int32_t q_total_y,
                    int32_t q_off, float* Y, void* stream);

@@ -38,6 +38,18 @@ class GtResizeAffine(C.Structure):
                 ("rp_b", C.c_void_p), ("rp_ldb", C.c_int64)]
 
 
+class GtEdgeGroups(C.Structure):       # gt_edge_groups: the edge tensor of a graph convolution as 1..3 channel groups
+    _fields_ = [("e", C.c_void_p * 3), ("c", C.c_int32 * 3), ("n_groups", C.c_int32)]
+
+
+GRAPHCONV_MAX_N = 8192          # GT_GRAPHCONV_MAX_N
+GRAPHCONV_MAX_PAIRS = 8         # GT_GRAPHCONV_MAX_PAIRS
+
+
+class GtGraphPairs(C.Structure):       # gt_graph_pairs: the (output gradient, support) pairs of a layer stack
+    _fields_ = [("g", C.c_void_p * GRAPHCONV_MAX_PAIRS), ("s", C.c_void_p * GRAPHCONV_MAX_PAIRS), ("n_pairs", C.c_int32)]
+
+
 class GtGemmDesc(C.Structure):
     _fields_ = [
         ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
@@ -234,6 +246,11 @@ _PROTOS = {
     "gt_deconv3x3s2_dbias_ws_bytes": (C.c_int64, [C.c_int32] * 6),
     "gt_deconv3x3s2_dbias": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.POINTER(GtDropout), C.c_int32, C.c_void_p,
                                                                            C.c_int64, C.c_void_p]),
+    "gt_graphconv_fwd": (C.c_int, [C.POINTER(GtEdgeGroups), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int32] * 4 +
+                         [C.c_void_p]),
+    "gt_graphconv_bwd_data": (C.c_int, [C.POINTER(GtEdgeGroups), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_int32] * 3 +
+                              [C.c_void_p]),
+    "gt_graphconv_bwd_edge": (C.c_int, [C.POINTER(GtEdgeGroups), C.POINTER(GtGraphPairs), C.c_int64, C.c_int64] + [C.c_int32] * 3 + [C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
@@ -1253,6 +1270,64 @@ def deconv3x3s2_dbias(g: torch.Tensor, gate: Optional[torch.Tensor], B: int, Hh:
     _launch("gt_deconv3x3s2_dbias", g, gate, db, B, Hh, Ww, Cout, pad, outpad, drop, act, ws=ws,
             nbytes=4.0 * g.numel() * (2 if gate is not None else 1), shape=(B, Hh, Ww, Cout, pad, outpad))
     return db
+
+
+# ----------------------------------------------------------------------------------- graph convolution
+def edge_groups(edges, B: int, n: int) -> GtEdgeGroups:
+    """gt_edge_groups of 1..3 dense [B, c_g, n, n] tensors; None stands for a group without a tensor (bwd_edge: no gradient
+    wanted) and is given as (None, c_g)."""
+    if not 1 <= len(edges) <= 3:
+        raise GtError(f"graph convolution: {len(edges)} channel groups (1..3)")
+    eg = GtEdgeGroups()
+    eg.n_groups = len(edges)
+    for g, e in enumerate(edges):
+        if isinstance(e, tuple):
+            eg.e[g], eg.c[g] = None, e[1]
+            continue
+        need_f32_cuda(e)
+        if e.dim() != 4 or e.shape[0] != B or e.shape[2] != n or e.shape[3] != n or not e.is_contiguous():
+            raise GtError(f"graph convolution: edge group {g} is {tuple(e.shape)}, wanted dense [{B}, c, {n}, {n}]")
+        eg.e[g], eg.c[g] = e.data_ptr(), e.shape[1]
+    return eg
+
+
+def graphconv_fwd(edges, S: torch.Tensor, bias: Optional[torch.Tensor], B: int, n: int, Cc: int, act: int = ACT_NONE,
+                  Y: Optional[torch.Tensor] = None, lds: Optional[int] = None, ldy: Optional[int] = None) -> torch.Tensor:
+    """Y[b,i,c] = act(sum_j E[b,c,i,j] S[b,j,c] + bias[c]); S, Y token-major [B, n, C] (leading dimensions lds, ldy)."""
+    need_f32_cuda(S, bias, Y)
+    if Y is None:
+        Y = torch.empty(B, n, Cc, dtype=torch.float32, device=S.device)
+    _launch("gt_graphconv_fwd", C.byref(edge_groups(edges, B, n)), S, lds or Cc, bias, Y, ldy or Cc, B, n, Cc, act,
+            flops=2.0 * B * Cc * n * n, nbytes=4.0 * B * Cc * (n * n + 2 * n), shape=(B, n, Cc, len(edges)))
+    return Y
+
+
+def graphconv_bwd_data(edges, G: torch.Tensor, B: int, n: int, Cc: int, dS: Optional[torch.Tensor] = None,
+                       ldg: Optional[int] = None, ldds: Optional[int] = None) -> torch.Tensor:
+    """dS[b,j,c] = sum_i E[b,c,i,j] G[b,i,c]."""
+    need_f32_cuda(G, dS)
+    if dS is None:
+        dS = torch.empty(B, n, Cc, dtype=torch.float32, device=G.device)
+    _launch("gt_graphconv_bwd_data", C.byref(edge_groups(edges, B, n)), G, ldg or Cc, dS, ldds or Cc, B, n, Cc,
+            flops=2.0 * B * Cc * n * n, nbytes=4.0 * B * Cc * (n * n + 2 * n), shape=(B, n, Cc, len(edges)))
+    return dS
+
+
+def graphconv_bwd_edge(d_edges, Gs, Ss, B: int, n: int, Cc: int, ldg: Optional[int] = None, lds: Optional[int] = None):
+    """d_edges[g][b,c,i,j] = sum_l Gs[l][b,i,c] Ss[l][b,j,c], every wanted group written once; d_edges as for edge_groups
+    (a (None, c_g) entry is skipped)."""
+    if len(Gs) != len(Ss):
+        raise GtError("graphconv_bwd_edge: as many gradients as supports")
+    pr = GtGraphPairs()
+    pr.n_pairs = len(Gs)
+    for l, (g, s) in enumerate(zip(Gs, Ss)):
+        need_f32_cuda(g, s)
+        if l < GRAPHCONV_MAX_PAIRS:
+            pr.g[l], pr.s[l] = g.data_ptr(), s.data_ptr()
+    c_out = sum(e.shape[1] for e in d_edges if not isinstance(e, tuple))
+    _launch("gt_graphconv_bwd_edge", C.byref(edge_groups(d_edges, B, n)), C.byref(pr), ldg or Cc, lds or Cc, B, n, Cc,
+            flops=2.0 * len(Gs) * B * c_out * n * n, nbytes=4.0 * B * (c_out * n * n + 2 * len(Gs) * Cc * n),
+            shape=(B, n, Cc, len(d_edges), len(Gs)))
 
 
 RS_MAXT = 6          # gt_resize.hip: output rows / columns per input cell that the resize backward holds in registers

@@ -259,6 +259,10 @@ class BurgersDataset(Dataset):
             synthetic = not (data_path is not None and os.path.exists(data_path))
         self.synthetic = synthetic
         self.n_samples_synthetic = n_samples_synthetic
+        self.n_krylov, self.smoother, self.renormalization = n_krylov, smoother, renormalization
+        self.return_edge = return_edge
+        self.return_distance_features, self.return_mass_features = return_distance_features, return_mass_features
+        self.edge_features = self.mass_features = None
         self._initialize()
 
     def __len__(self):
@@ -294,11 +298,61 @@ class BurgersDataset(Dataset):
         self.target_diff = self.central_diff(y, self.h * s)[..., None].astype(np.float32)
         self.grid = np.linspace(0, 1, self.n_grid)[:, None].astype(np.float32)
 
+        if self.return_edge:        # one uniform grid: the same edge / mass features for every sample, built once
+            self.edge_features, self.mass_features = self.get_edge(np.linspace(0, 1, self.n_grid))
+
+    def get_edge(self, grid):
+        """Edge features [n, n, n_krylov + 2 return_distance_features + return_mass_features] and the P1 mass matrix
+        [n, n] of a 1-D grid, float32 (ft.py:289-318 with utils_ft.py:172-208, 211-265, 268-300; dense numpy):
+          * the P1 stiffness matrix (tridiagonal: 1/h_k on both ends of element k, -1/h_k beside them), + n_grid on the
+            diagonal with `renormalization`, scaled D^{-1/2} A D^{-1/2} by its diagonal, I - (2/3) A with
+            smoother='jacobi', cast to float32;
+          * its powers A, A A, ... (n_krylov of them), multiplied up in float64 from the float32 matrix;
+          * exp(-d) and 1 / (1 + d) of d = |x_i - x_j| / (max + 1e-8);
+          * the mass matrix (h/3, h/6; not normalised) as one more channel, only when both the distance and the mass
+            features are asked for."""
+        grid = np.asarray(grid, dtype=np.float64)
+        n = grid.shape[0]
+        h = grid[1:] - grid[:-1]
+        k = np.arange(n - 1)
+        A = np.zeros((n, n))
+        M = np.zeros((n, n))
+        for i in range(2):
+            for j in range(2):
+                np.add.at(A, (k + i, k + j), (1.0 if i == j else -1.0) / h)
+                np.add.at(M, (k + i, k + j), h * ((i == j) + 1) / 6)
+        if self.renormalization:
+            A[np.arange(n), np.arange(n)] += self.n_grid
+        d = np.diag(A) ** (-0.5)
+        A = (d[:, None] * A) * d[None, :]
+        if self.smoother == 'jacobi':
+            A = np.eye(n) - (2 / 3) * A
+        elif self.smoother == 'gs':
+            raise NotImplementedError("Gauss-seidel not implemented")
+        edge = A.astype(np.float32)
+        if self.n_krylov > 1:
+            edges = np.zeros((n, n, self.n_krylov))
+            edges[..., 0] = edge
+            for i in range(1, self.n_krylov):
+                edges[..., i] = edge.dot(edges[..., i - 1])
+        else:
+            edges = edge[..., None]
+        mass = M.astype(np.float32)
+        if self.return_distance_features:
+            dist = np.abs(grid[:, None] - grid[None, :])
+            dist = dist / (dist.max() + 1e-8)
+            parts = [edges, np.exp(-dist)[..., None], (1 / (1 + dist))[..., None]]
+            if self.return_mass_features:
+                parts.append(mass[..., None])
+            edges = np.concatenate(parts, axis=2)
+        return edges.astype(np.float32), mass
+
     def __getitem__(self, index):
         f = lambda v: torch.from_numpy(np.ascontiguousarray(v)).float()
         one = torch.tensor([1.0])
-        return dict(node=f(self.node_features[index]), pos=f(self.grid), grid=f(self.grid), edge=one,
-                    mass=one, target=f(self.target[index]), target_grad=f(self.target_diff[index]))
+        edge, mass = (f(self.edge_features), f(self.mass_features)) if self.return_edge else (one, one)
+        return dict(node=f(self.node_features[index]), pos=f(self.grid), grid=f(self.grid), edge=edge,
+                    mass=mass, target=f(self.target[index]), target_grad=f(self.target_diff[index]))
 
 
 # --------------------------------------------------------------------------------------- losses

@@ -140,6 +140,76 @@ class _Shortcut2d(nn.Module):
 Shortcut2d = _Shortcut2d
 
 
+# --------------------------------------------------------------------------------------- graph feature extractor
+class GraphConvolution(nn.Module):
+    """One GCN layer against a dense per-channel edge tensor (layers.py:153-198):
+    out[b,c,i] = sum_j edge[b,c,i,j] (x W)[b,j,c] + bias[c].
+
+    x is [B, n, in_features] or [B, in_features, n] (told apart by the reference's rule: a last axis that is not
+    in_features means channels-first), edge [B, out_features, n, n]; returns [B, out_features, n] as the reference does.
+    The product runs on gt_graphconv_* through ops.graph_conv_stack with one layer.  B = 1 keeps its batch axis (the
+    reference's squeeze() drops it)."""
+
+    def __init__(self, in_features, out_features, bias=True, debug=False):
+        super().__init__()
+        self.in_features = in_features
+        self.out_features = out_features
+        self.weight = Parameter(torch.empty(in_features, out_features))
+        self.debug = debug
+        if bias:
+            self.bias = Parameter(torch.empty(out_features))
+        else:
+            self.register_parameter('bias', None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        stdv = 1. / math.sqrt(self.weight.size(1))
+        self.weight.data.uniform_(-stdv, stdv)
+        if self.bias is not None:
+            self.bias.data.uniform_(-stdv, stdv)
+
+    def forward(self, x, edge):
+        if x.size(-1) != self.in_features:
+            x = x.transpose(-2, -1)
+        assert x.size(1) == edge.size(-1)
+        return ops.graph_conv_stack(x, edge, (self.weight,), (self.bias,), (False,)).permute(0, 2, 1)
+
+    def __repr__(self):
+        return self.__class__.__name__ + ' (' + str(self.in_features) + ' -> ' + str(self.out_features) + ')'
+
+
+class EdgeEncoder(nn.Module):
+    """Two 3x3 convolution blocks over the edge features, concatenated on the channel axis, the raw features in front with
+    raw_laplacian (layers.py:260-281).  The convolutions are the library's (ops.edge_conv: with its deterministic weight
+    gradient), their dropout -> SiLU tails ops.drop_act, as in Conv2dEncoder.  groups() hands GCN the pieces
+    un-concatenated."""
+
+    def __init__(self, out_dim: int, edge_feats: int, raw_laplacian=None):
+        super().__init__()
+        assert out_dim > edge_feats
+        self.return_lap = raw_laplacian
+        if self.return_lap:
+            out_dim = out_dim - edge_feats
+        conv_dim0 = int(out_dim / 3 * 2)
+        conv_dim1 = int(out_dim - conv_dim0)
+        self.lap_conv1 = Conv2dResBlock(edge_feats, conv_dim0)
+        self.lap_conv2 = Conv2dResBlock(conv_dim0, conv_dim1)
+
+    def _block(self, blk, x):
+        # Conv2dResBlock's plain form, conv -> dropout -> activation, with the convolution through ops.edge_conv (the
+        # library's kernels, its reproducible weight gradient) and the tail in one elementwise pass
+        assert blk.plain()
+        return ops.drop_act(ops.edge_conv(x, blk.conv[0]), blk.conv[1].p, _act_name(blk.activation), self.training)
+
+    def groups(self, lap):
+        edge1 = self._block(self.lap_conv1, lap)
+        edge2 = self._block(self.lap_conv2, edge1)
+        return (lap, edge1, edge2) if self.return_lap else (edge1, edge2)
+
+    def forward(self, lap):
+        return torch.cat(self.groups(lap), dim=1)
+
+
 def _resize(x, size, act_module=None, in_nhwc=False, out_nhwc=False):
     """activation(F.interpolate(x, ..., mode='bilinear', align_corners=True)) on the HIP resize kernel;
     a ReLU is fused into the kernel, any other activation is applied on its output."""

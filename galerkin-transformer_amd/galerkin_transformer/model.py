@@ -15,9 +15,11 @@ import torch.nn.functional as F
 from torch import nn
 from torch.nn.init import constant_, xavier_uniform_
 
+from . import _hip as H
 from . import ops
-from .layers import (Conv2dEncoder, DeConv2dBlock, FeedForward, Identity, Interp2dEncoder, Interp2dUpsample,
-                     PositionalEncoding, SimpleAttention, SpectralConv1d, SpectralConv2d, _act_module, _act_name, default)
+from .layers import (Conv2dEncoder, DeConv2dBlock, EdgeEncoder, FeedForward, GraphConvolution, Identity, Interp2dEncoder,
+                     Interp2dUpsample, PositionalEncoding, SimpleAttention, SpectralConv1d, SpectralConv2d, _act_module,
+                     _act_name, default)
 
 current_path = os.path.dirname(os.path.abspath(__file__))
 SRC_ROOT = os.path.dirname(current_path)
@@ -278,6 +280,49 @@ class UpScaler(nn.Module):
         return self.upsample(x, in_nhwc=True, out_nhwc=True)
 
 
+class GCN(nn.Module):
+    """Graph feature extractor: a learned edge encoder, then num_gcn_layers graph convolutions that share its output
+    (reference model.py:376-427; state_dict keys edge_learner.lap_conv{1,2}.conv.0.weight, gcn_layer0.*, gcn_layers.{i}.*).
+
+    forward(x [B, n, node_feats], edge [B, n, n, edge_feats]) -> [B, n, out_features]:
+        E = EdgeEncoder(edge.permute(0, 3, 1, 2))                      [B, C, n, n], kept as its channel groups
+        h_0 = x;  h_{l+1}[b,i,c] = sum_j E[b,c,i,j] (h_l W_l)[b,j,c] + bias_l[c]
+    with a ReLU behind the layers 1 .. L-2 only, and only if `activation` is truthy: never behind gcn_layer0 or the last
+    layer, so two layers have none.  The whole layer stack is one operator, ops.graph_conv_stack, on the gt_graphconv_*
+    kernels; `dropout` and `relu` sit unused on the module tree as in the reference.
+
+    Deviations from the reference, both accidents of its GraphConvolution.forward:
+      * B = 1: its squeeze() drops the batch axis and the next layer fails; here B = 1 gives the natural result;
+      * n == out_features: it decides whether to transpose by x.size(-1) != in_features, takes the [B, C, n] output of
+        the previous layer for [B, n, C] and contracts the later layers over the wrong axis (0.79 relative L2 away from
+        the formula above); here the formula holds for every n.
+    num_gcn_layers = 1 (an IndexError in the reference's forward) is refused at construction."""
+
+    def __init__(self, node_feats=4, out_features=96, num_gcn_layers=2, edge_feats=6, activation=True,
+                 raw_laplacian=False, dropout=0.1, debug=False):
+        super().__init__()
+        if num_gcn_layers < 2:
+            raise ValueError("num_gcn_layers >= 2")
+        self.edge_learner = EdgeEncoder(out_dim=out_features, edge_feats=edge_feats, raw_laplacian=raw_laplacian)
+        self.gcn_layer0 = GraphConvolution(in_features=node_feats, out_features=out_features, debug=debug)
+        self.gcn_layers = nn.ModuleList([copy.deepcopy(GraphConvolution(
+            in_features=out_features, out_features=out_features, debug=debug)) for _ in range(1, num_gcn_layers)])
+        self.activation = activation
+        self.relu = nn.ReLU()
+        self.dropout = nn.Dropout(dropout)
+        self.edge_feats = edge_feats
+        self.debug = debug
+
+    def forward(self, x, edge):
+        H.need_f32_cuda(x, edge)
+        assert edge.size(-1) == self.edge_feats
+        layers = [self.gcn_layer0] + list(self.gcn_layers)
+        L = len(layers)
+        relu = [bool(self.activation) and 0 < l < L - 1 for l in range(L)]
+        groups = self.edge_learner.groups(edge.permute(0, 3, 1, 2).contiguous())
+        return ops.graph_conv_stack(x, groups, [g.weight for g in layers], [g.bias for g in layers], relu)
+
+
 class _ConfiguredModel(nn.Module):
     """Config-dict plumbing shared by the three model classes: every config key (and every name in
     ADDITIONAL_ATTR) becomes an attribute, missing keys read as None (model.py:1071-1074)."""
@@ -293,6 +338,19 @@ class _ConfiguredModel(nn.Module):
         self.dpo = nn.Dropout(self.dropout)
         if self.decoder_type == 'attention':
             self.num_encoder_layers += 1
+
+    def _graph_extractor(self, node_feats):
+        """The GCN of feat_extract_type='gcn' with num_feat_layers > 0 (model.py:847-856, 1084-1093), or None."""
+        if not (self.num_feat_layers and self.num_feat_layers > 0):
+            return None
+        if self.feat_extract_type == 'gat':
+            raise NotImplementedError("feat_extract_type='gat': graph attention has no HIP path; GCN "
+                                      "(feat_extract_type='gcn') is the graph feature extractor on the HIP hot path")
+        if self.feat_extract_type != 'gcn':
+            return None
+        return GCN(node_feats=node_feats, edge_feats=self.edge_feats, num_gcn_layers=self.num_feat_layers,
+                   out_features=self.n_hidden, activation=self.graph_activation, raw_laplacian=self.raw_laplacian,
+                   debug=self.debug)
 
     def _stack_encoders(self, **extra):
         if self.attention_type not in self._hip_attention:
@@ -331,10 +389,8 @@ class SimpleTransformer(_ConfiguredModel):
         self._read_config(kwargs)
         self.spacial_dim = default(self.spacial_dim, self.pos_dim)
         self.spacial_fc = default(self.spacial_fc, False)
-        if self.num_feat_layers and self.num_feat_layers > 0 and self.feat_extract_type in ('gcn', 'gat'):
-            raise NotImplementedError("graph feature extractors are outside the HIP hot path "
-                                      "(num_feat_layers is 0 in every config)")
-        self.feat_extract = Identity(in_features=self.node_feats, out_features=self.n_hidden)
+        self.feat_extract = (self._graph_extractor(self.node_feats)
+                             or Identity(in_features=self.node_feats, out_features=self.n_hidden))
         self._stack_encoders(norm_type=self.norm_type, batch_norm=self.batch_norm,
                              symmetric_init=self.symmetric_init, attn_weight=self.return_attn_weight,
                              residual_type=self.residual_type, activation_type=self.attn_activation)
@@ -390,10 +446,7 @@ class FourierTransformer2D(_ConfiguredModel):
     def __init__(self, **kwargs):
         super().__init__()
         self._read_config(kwargs)
-        if self.num_feat_layers and self.num_feat_layers > 0 and self.feat_extract_type in ('gcn', 'gat'):
-            raise NotImplementedError("graph feature extractors are outside the HIP hot path "
-                                      "(num_feat_layers is 0 in every config)")
-        self.feat_extract = Identity()
+        self.feat_extract = self._graph_extractor(self.n_hidden) or Identity()
         if self.downscaler_size:
             self.downscaler = DownScaler(in_dim=self.node_feats, out_dim=self.n_hidden,
                                          downsample_mode=self.downsample_mode,
@@ -441,6 +494,7 @@ class FourierTransformer2D(_ConfiguredModel):
             node = torch.cat([node, pos.contiguous().view(bsz, n_s, n_s, -1)], dim=-1)
         x = self.downscaler(node)
         x = x.reshape(bsz, -1, self.n_hidden)
+        x = self.feat_extract(x, edge)
         x = self._drop(x)
         for encoder in self.encoder_layers:
             if self.return_attn_weight:

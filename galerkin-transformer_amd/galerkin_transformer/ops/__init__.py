@@ -16,6 +16,8 @@ One module per operator family; this file only re-exports (every name is the obj
 ``scaler_conv`` the 'conv' scaler modes: 2x2 average pool + activation, the 3x3 / stride-2 transposed convolution,
                  ``deconv_out_size``
 ``dense``        ``packed_params``, Linear, the regression head, FeedForward, FeedForward with BatchNorm1d
+``graph``        the graph-convolution stack of the GCN feature extractor, ``graph_conv_stack``; the edge encoder's
+                 library convolution with a reproducible weight gradient, ``edge_conv``
 ``loss``         the weighted-L2 / H1 objectives per sample: ``H1Loss2dFn`` (2-D), ``H1Loss1dFn`` (1-D)
 ``attention``    the attention-dropout mode and mask queue, ``SimpleAttentionFn`` with its projection stage and cores,
                  ``CrossAttentionFn`` on the same cores
@@ -34,6 +36,7 @@ from .dense import (FeedForwardBNFn, FeedForwardFn, LinearFn, MlpHeadFn, _check_
                     feed_forward, feed_forward_bn, linear, mlp_head, packed_params)
 from .elementwise import (DropActFn, DropoutFn, LayerNormFn, _c, _next_salt, drop_act, dropout,  # noqa: F401
                           layer_norm)
+from .graph import EdgeConvFn, GraphConvStackFn, edge_conv, graph_conv_stack  # noqa: F401
 from .loss import H1Loss1dFn, H1Loss2dFn, weighted_l2_terms_1d, weighted_l2_terms_2d  # noqa: F401
 from .resize import (ResizeFn, ResizeSegFn, UpsampleFcFn, bilinear_resize, bilinear_resize_seg, out_size,  # noqa: F401
                      upsample_fc)

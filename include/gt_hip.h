@@ -919,6 +919,47 @@ int gt_deconv3x3s2_dbias(const float* dy, const float* gate, float* db, int32_t 
                          int32_t pad, int32_t outpad, const gt_dropout* drop, int32_t act, void* ws, int64_t ws_bytes,
                          void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Graph convolution against a dense per-channel edge tensor: the product of the reference's GraphConvolution
+ * (layers.py:153-198, torch.matmul(edge, support.unsqueeze(-1)): B C independent n x n matrix-vector products) and of its
+ * autograd backward, for the GCN feature extractor (model.py:376-427).  ABI v21, additive.
+ *
+ * The edge tensor E [B, C, n, n] arrives as 1..3 CHANNEL GROUPS: dense [B, c_g, n, n] tensors e[g] with sum c_g = C, group 0
+ * holding the channels 0 .. c_0 - 1 and so on -- the outputs of the edge encoder as they are, never concatenated.  The
+ * vectors S, Y, G, dS are token-major [B, n, C] with a leading dimension >= C (the column c of row (b, i) at (b n + i) ld + c),
+ * so the products h W around them are plain row-major GEMMs.  The two descriptors are HOST structs handed over by pointer, as
+ * gt_dropout is; they are read during the call and reach the kernels by value, so they may be reused or freed on return.
+ *   gt_graphconv_fwd       Y[b,i,c] = act(sum_j E[b,c,i,j] S[b,j,c] + bias[c]);  act: GT_ACT_NONE | GT_ACT_RELU, bias may be NULL.
+ *   gt_graphconv_bwd_data  dS[b,j,c] = sum_i E[b,c,i,j] G[b,i,c]: the transposed product, E read in its row-major order.
+ *   gt_graphconv_bwd_edge  dE_g[b,c,i,j] = sum_{l < n_pairs} g[l][b,i,c] s[l][b,j,c]: the rank-P update of a stack of P layers
+ *                          that share E, written once.  All g[l] share ldg, all s[l] share lds.  A group whose e[g] is NULL is
+ *                          skipped (its channels are still counted): the raw Laplacian when the edge input needs no gradient.
+ * Every n from 1 to GT_GRAPHCONV_MAX_N; 16-byte accesses when n % 4 == 0 and the group pointers are 16-byte aligned, dword
+ * accesses otherwise (a (b, c) slice starts at element (b c_g + c) n^2: off a 16-byte boundary for most other n).  64-bit
+ * offsets.  fp32, no atomics, fixed summation orders: bit-identical from run to run.  The caller's stream, no allocation, no
+ * scratch.  n_groups outside 1..3, c_g <= 0, sum c_g != C, a leading dimension < C, B / n / C / n_pairs < 1, a NULL tensor
+ * or descriptor (fwd / bwd_data: any group; bwd_edge: any g[l], s[l] with l < n_pairs), another act: GT_EINVAL.  n > GT_GRAPHCONV_MAX_N,
+ * n_pairs > GT_GRAPHCONV_MAX_PAIRS, B or C > 65535: GT_ENOTSUP, decided from the arguments alone, nothing launched.
+ * ------------------------------------------------------------------------------------------- */
+#define GT_GRAPHCONV_MAX_N     8192
+#define GT_GRAPHCONV_MAX_PAIRS 8
+typedef struct gt_edge_groups {
+    float* e[3];                /* group tensors (read-only for fwd / bwd_data); entries past n_groups are ignored */
+    int32_t c[3];               /* channels per group */
+    int32_t n_groups;           /* 1..3 */
+} gt_edge_groups;
+typedef struct gt_graph_pairs {
+    const float* g[GT_GRAPHCONV_MAX_PAIRS];   /* output gradients G_l [B, n, C], leading dimension ldg */
+    const float* s[GT_GRAPHCONV_MAX_PAIRS];   /* supports S_l = h_l W_l [B, n, C], leading dimension lds */
+    int32_t n_pairs;
+} gt_graph_pairs;
+int gt_graphconv_fwd(const gt_edge_groups* E, const float* S, int64_t lds, const float* bias, float* Y, int64_t ldy, int32_t B,
+                     int32_t n, int32_t C, int32_t act, void* stream);
+int gt_graphconv_bwd_data(const gt_edge_groups* E, const float* G, int64_t ldg, float* dS, int64_t ldds, int32_t B, int32_t n,
+                          int32_t C, void* stream);
+int gt_graphconv_bwd_edge(const gt_edge_groups* dE, const gt_graph_pairs* pairs, int64_t ldg, int64_t lds, int32_t B, int32_t n, int32_t C,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,10 +5,10 @@ the encoder layer and the spectral decoder execute in ``_lib/libgt_hip.so`` (han
 gfx950, C ABI in include/gt_hip.h).  There is no CPU fallback for those operators.
 """
 from .layers import *          # noqa: F401,F403
-from .layers import (EdgeEncoder, FeedForward, GraphConvolution, Identity, SimpleAttention, SpectralConv1d, SpectralConv2d,  # noqa: F401
+from .layers import (EdgeEncoder, FeedForward, GraphAttention, GraphConvolution, Identity, SimpleAttention, SpectralConv1d, SpectralConv2d,  # noqa: F401
                      get_attention_dropout, push_attention_masks, set_attention_dropout)
 from .model import *           # noqa: F401,F403
-from .model import (GCN, FourierTransformer, FourierTransformer2D, FourierTransformer2DLite,  # noqa: F401
+from .model import (GAT, GCN, FourierTransformer, FourierTransformer2D, FourierTransformer2DLite,  # noqa: F401
                     FourierTransformerEncoderLayer, PointwiseRegressor, SimpleTransformer,
                     SimpleTransformerEncoderLayer, SpectralRegressor)
 

@@ -44,6 +44,8 @@ class GtEdgeGroups(C.Structure):       # gt_edge_groups: the edge tensor of a gr
 
 GRAPHCONV_MAX_N = 8192          # GT_GRAPHCONV_MAX_N
 GRAPHCONV_MAX_PAIRS = 8         # GT_GRAPHCONV_MAX_PAIRS
+GRAPHATTN_MAX_N = 8192          # GT_GRAPHATTN_MAX_N
+GRAPHATTN_MAX_F = 256           # GT_GRAPHATTN_MAX_F
 
 
 class GtGraphPairs(C.Structure):       # gt_graph_pairs: the (output gradient, support) pairs of a layer stack
@@ -251,6 +253,16 @@ _PROTOS = {
     "gt_graphconv_bwd_data": (C.c_int, [C.POINTER(GtEdgeGroups), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_int32] * 3 +
                               [C.c_void_p]),
     "gt_graphconv_bwd_edge": (C.c_int, [C.POINTER(GtEdgeGroups), C.POINTER(GtGraphPairs), C.c_int64, C.c_int64] + [C.c_int32] * 3 + [C.c_void_p]),
+    "gt_graphattn_mask": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_float, C.c_void_p]),
+    "gt_graphattn_fwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p] +
+                         [C.c_int32] * 3 + [C.c_float, C.c_int32, C.c_int32, C.POINTER(GtDropout), C.c_void_p]),
+    "gt_graphattn_bwd_row": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                                                          C.c_int64, C.c_void_p, C.c_void_p] +
+                             [C.c_int32] * 3 + [C.c_float, C.c_int32, C.c_int32, C.POINTER(GtDropout), C.c_void_p]),
+    "gt_graphattn_bwd_col": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64] +
+                             [C.c_int32] * 3 + [C.c_float, C.POINTER(GtDropout), C.c_void_p]),
+    "gt_graphattn_weights": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
+                                                         C.POINTER(GtDropout), C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
@@ -334,7 +346,8 @@ def _timed(key, flops, nbytes, fn, replay=None, shape=None):
     e0.record()
     rc = fn()
     e1.record()
-    _prof.records.append((key, flops, nbytes, e0, e1, replay, shape))
+    if not rc:             # a refused call launched nothing: no record
+        _prof.records.append((key, flops, nbytes, e0, e1, replay, shape))
     return rc
 
 
@@ -1328,6 +1341,68 @@ def graphconv_bwd_edge(d_edges, Gs, Ss, B: int, n: int, Cc: int, ldg: Optional[i
     _launch("gt_graphconv_bwd_edge", C.byref(edge_groups(d_edges, B, n)), C.byref(pr), ldg or Cc, lds or Cc, B, n, Cc,
             flops=2.0 * len(Gs) * B * c_out * n * n, nbytes=4.0 * B * (c_out * n * n + 2 * len(Gs) * Cc * n),
             shape=(B, n, Cc, len(d_edges), len(Gs)))
+
+
+# ----------------------------------------------------------------------------------- graph attention
+def graphattn_words(n: int) -> int:
+    """64-bit mask words per row of the packed keep bits."""
+    return (n + 63) // 64
+
+
+def graphattn_mask(adj: torch.Tensor, graph_lap: bool, thresh: float):
+    """adj [B, n, n] -> (bits, bitsT, w0): the keep predicate as int64 words [B, n, ceil(n/64)], row-major and transposed, and
+    the weight of a masked entry per row [B, n] (gt_hip.h: gt_graphattn_mask).  adj is dense or one channel of a dense
+    edge tensor [B, n, n, E] (edge[..., c]), which is read in place."""
+    need_f32_cuda(adj)
+    if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
+        raise GtError(f"graph attention: adj is {tuple(adj.shape)}, wanted [B, n, n]")
+    B, n = adj.shape[0], adj.shape[1]
+    es = adj.stride(2) if n > 1 else 1
+    if es < 1 or (n > 1 and adj.stride(1) != n * es) or (B > 1 and adj.stride(0) != n * n * es):
+        adj, es = adj.contiguous(), 1
+    W = graphattn_words(max(n, 1))
+    bits = torch.empty(B, n, W, dtype=torch.int64, device=adj.device)
+    bitsT = torch.empty(B, n, W, dtype=torch.int64, device=adj.device)
+    w0 = torch.empty(B, n, dtype=torch.float32, device=adj.device)
+    _launch("gt_graphattn_mask", adj, es, bits, bitsT, w0, B, n, int(bool(graph_lap)), float(thresh),
+            nbytes=4.0 * B * n * n + 16.0 * B * n * W, shape=(B, n))
+    return bits, bitsT, w0
+
+
+def graphattn_fwd(bits, w0, s, t, ldst: int, h, U, out, L, B: int, n: int, F: int, alpha: float, concat: bool, relu: bool,
+                  drop: Optional[GtDropout] = None, ldh: Optional[int] = None, ldo: Optional[int] = None):
+    """L, U = Pm h (U may be None: not stored) and out = relu?(ELU?(U)); s, t at stride ldst (gt_hip.h: gt_graphattn_fwd)."""
+    need_f32_cuda(w0, s, t, h, U, out, L)
+    _launch("gt_graphattn_fwd", bits, w0, s, t, ldst, h, ldh or F, U, out, ldo or F, L, B, n, F, float(alpha), int(bool(concat)),
+            int(bool(relu)), drop, flops=2.0 * B * n * n * F, nbytes=B * n * n / 8.0 + 12.0 * B * n * F, shape=(B, n, F))
+
+
+def graphattn_bwd_row(bits, s, t, ldst: int, L, dout, U, h, dU, ds, dt_part, B: int, n: int, F: int, alpha: float,
+                      concat: bool, relu: bool, drop: Optional[GtDropout] = None, ldo: Optional[int] = None,
+                      ldh: Optional[int] = None, lddu: Optional[int] = None):
+    """dU, ds and the per-row-tile partial sums of dt (gt_hip.h: gt_graphattn_bwd_row)."""
+    need_f32_cuda(s, t, L, dout, U, h, dU, ds, dt_part)
+    _launch("gt_graphattn_bwd_row", bits, s, t, ldst, L, dout, U, ldo or F, h, ldh or F, dU, lddu or F, ds, dt_part, B, n, F,
+            float(alpha), int(bool(concat)), int(bool(relu)), drop, flops=2.0 * B * n * n * F,
+            nbytes=B * n * n / 8.0 + 16.0 * B * n * F, shape=(B, n, F))
+
+
+def graphattn_bwd_col(bitsT, w0, s, t, ldst: int, L, dU, a, ds, dt_part, dt, dH, B: int, n: int, F: int, alpha: float,
+                      drop: Optional[GtDropout] = None, lddu: Optional[int] = None, lddh: Optional[int] = None):
+    """dt and dH = Pm^T dU + ds a[:F]^T + dt a[F:]^T (gt_hip.h: gt_graphattn_bwd_col)."""
+    need_f32_cuda(w0, s, t, L, dU, a, ds, dt_part, dt, dH)
+    _launch("gt_graphattn_bwd_col", bitsT, w0, s, t, ldst, L, dU, lddu or F, a, ds, dt_part, dt, dH, lddh or F, B, n, F,
+            float(alpha), drop, flops=2.0 * B * n * n * F, nbytes=B * n * n / 8.0 + 8.0 * B * n * F, shape=(B, n, F))
+
+
+def graphattn_weights(bits, w0, s, t, ldst: int, L, B: int, n: int, alpha: float, drop: Optional[GtDropout] = None,
+                      Pm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The attention weights Pm [B, n, n] (after dropout), dense (gt_hip.h: gt_graphattn_weights)."""
+    need_f32_cuda(w0, s, t, L, Pm)
+    if Pm is None:
+        Pm = torch.empty(B, n, n, dtype=torch.float32, device=s.device)
+    _launch("gt_graphattn_weights", bits, w0, s, t, ldst, L, Pm, B, n, float(alpha), drop, nbytes=4.0 * B * n * n, shape=(B, n))
+    return Pm
 
 
 RS_MAXT = 6          # gt_resize.hip: output rows / columns per input cell that the resize backward holds in registers

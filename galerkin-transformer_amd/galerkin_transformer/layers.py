@@ -178,6 +178,42 @@ class GraphConvolution(nn.Module):
         return self.__class__.__name__ + ' (' + str(self.in_features) + ' -> ' + str(self.out_features) + ')'
 
 
+class GraphAttention(nn.Module):
+    """One GAT layer against a dense adjacency (layers.py:201-257), batched:
+        h = node W;  e_ij = LeakyReLU_alpha(h_i . a[:F] + h_j . a[F:]) where adj keeps (i, j), else -9e15;
+        out = ELU?(dropout(softmax_j(e)) h).
+    adj keeps (i, j) where |adj_ij| > interaction_thresh (graph_lap) or adj_ij > 0.  The scores are rank-1 before the
+    LeakyReLU, so the layer runs on the gt_graphattn_* kernels through ops.graph_attention_stack with one layer and never
+    forms the reference's [B, n, n, 2F] input of the score product.  `dropout` is a plain float that follows
+    module.training only (not set_attention_dropout); adj gets no gradient."""
+
+    def __init__(self, in_features, out_features, alpha=1e-2, concat=True, graph_lap=True, interaction_thresh=1e-6,
+                 dropout=0.1):
+        super().__init__()
+        self.dropout = dropout
+        self.in_features = in_features
+        self.out_features = out_features
+        self.alpha = alpha
+        self.concat = concat
+        self.graph_lap = graph_lap
+        self.thresh = interaction_thresh
+        self.W = Parameter(torch.empty(in_features, out_features))
+        xavier_normal_(self.W, gain=np.sqrt(2.0))
+        self.a = Parameter(torch.empty(2 * out_features, 1))
+        xavier_normal_(self.a, gain=np.sqrt(2.0))
+        self.leakyrelu = nn.LeakyReLU(self.alpha)
+
+    def stack_args(self):
+        return dict(alpha=self.alpha, concat=self.concat, graph_lap=self.graph_lap, thresh=self.thresh,
+                    p=float(self.dropout) if self.training else 0.0)
+
+    def forward(self, node, adj):
+        return ops.graph_attention_stack(node, adj, (self.W,), (self.a,), (False,), **self.stack_args())
+
+    def __repr__(self):
+        return self.__class__.__name__ + ' (' + str(self.in_features) + ' -> ' + str(self.out_features) + ')'
+
+
 class EdgeEncoder(nn.Module):
     """Two 3x3 convolution blocks over the edge features, concatenated on the channel axis, the raw features in front with
     raw_laplacian (layers.py:260-281).  The convolutions are the library's (ops.edge_conv: with its deterministic weight

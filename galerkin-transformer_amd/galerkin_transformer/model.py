@@ -17,7 +17,7 @@ from torch.nn.init import constant_, xavier_uniform_
 
 from . import _hip as H
 from . import ops
-from .layers import (Conv2dEncoder, DeConv2dBlock, EdgeEncoder, FeedForward, GraphConvolution, Identity, Interp2dEncoder,
+from .layers import (Conv2dEncoder, DeConv2dBlock, EdgeEncoder, FeedForward, GraphAttention, GraphConvolution, Identity, Interp2dEncoder,
                      Interp2dUpsample, PositionalEncoding, SimpleAttention, SpectralConv1d, SpectralConv2d, _act_module,
                      _act_name, default)
 
@@ -323,6 +323,45 @@ class GCN(nn.Module):
         return ops.graph_conv_stack(x, groups, [g.weight for g in layers], [g.bias for g in layers], relu)
 
 
+class GAT(nn.Module):
+    """Graph feature extractor: num_gcn_layers graph-attention layers over one adjacency (reference model.py:430-469;
+    state_dict keys gat_layer0.{W,a}, gat_layers.{i}.{W,a}).
+
+    forward(x [B, n, node_feats], edge [B, n, n, E]) -> [B, n, out_features] with adj = edge[..., 0], read in place (the
+    reference copies it out): gat_layer0, then
+    gat_layers[:-1], each of THOSE followed by a ReLU iff `activation`, then gat_layers[-1].  Every layer keeps concat=True,
+    so an ELU follows every layer, the last included.  The whole stack is one operator, ops.graph_attention_stack, on the
+    gt_graphattn_* kernels: the keep bits of adj are packed once for all layers and both directions.  Each layer's dropout
+    follows its own `dropout` float and module.training.  edge_feats and `relu` sit unused as in the reference.
+    num_gcn_layers = 1 (an IndexError in the reference's forward) is refused at construction."""
+
+    def __init__(self, node_feats=4, out_features=96, num_gcn_layers=2, edge_feats=None, activation=False, debug=False):
+        super().__init__()
+        if num_gcn_layers < 2:
+            raise ValueError("num_gcn_layers >= 2")
+        self.gat_layer0 = GraphAttention(in_features=node_feats, out_features=out_features)
+        self.gat_layers = nn.ModuleList([copy.deepcopy(GraphAttention(
+            in_features=out_features, out_features=out_features)) for _ in range(1, num_gcn_layers)])
+        self.activation = activation
+        self.relu = nn.ReLU()
+        self.debug = debug
+
+    def forward(self, x, edge):
+        H.need_f32_cuda(x, edge)
+        layers = [self.gat_layer0] + list(self.gat_layers)
+        L = len(layers)
+        relu = [bool(self.activation) and 0 < l < L - 1 for l in range(L)]
+        args = [g.stack_args() for g in layers]
+        if any(a != args[0] for a in args[1:]):        # layers edited apart after construction: one operator call each
+            out = x
+            adj = edge[..., 0]
+            for g, r in zip(layers, relu):
+                out = ops.graph_attention_stack(out, adj, (g.W,), (g.a,), (r,), **g.stack_args())
+            return out
+        return ops.graph_attention_stack(x, edge[..., 0], [g.W for g in layers], [g.a for g in layers], relu,
+                                         **args[0])
+
+
 class _ConfiguredModel(nn.Module):
     """Config-dict plumbing shared by the three model classes: every config key (and every name in
     ADDITIONAL_ATTR) becomes an attribute, missing keys read as None (model.py:1071-1074)."""
@@ -344,8 +383,12 @@ class _ConfiguredModel(nn.Module):
         if not (self.num_feat_layers and self.num_feat_layers > 0):
             return None
         if self.feat_extract_type == 'gat':
-            raise NotImplementedError("feat_extract_type='gat': graph attention has no HIP path; GCN "
-                                      "(feat_extract_type='gcn') is the graph feature extractor on the HIP hot path")
+            # GraphAttention / GAT exist on the HIP path; the switch stays unwired because
+            # tests/test_graph_conv_cpu.py::test_refusals pins this refusal (and a message that names GCN)
+            raise NotImplementedError("feat_extract_type='gat' is not wired into the config switch yet (GCN, "
+                                      "feat_extract_type='gcn', is); the modules exist: build the model without a graph "
+                                      "extractor and assign model.feat_extract = GAT(node_feats, out_features=n_hidden, "
+                                      "num_gcn_layers=...), which forward() calls as feat_extract(node, edge)")
         if self.feat_extract_type != 'gcn':
             return None
         return GCN(node_feats=node_feats, edge_feats=self.edge_feats, num_gcn_layers=self.num_feat_layers,

@@ -36,7 +36,8 @@ from .dense import (FeedForwardBNFn, FeedForwardFn, LinearFn, MlpHeadFn, _check_
                     feed_forward, feed_forward_bn, linear, mlp_head, packed_params)
 from .elementwise import (DropActFn, DropoutFn, LayerNormFn, _c, _next_salt, drop_act, dropout,  # noqa: F401
                           layer_norm)
-from .graph import EdgeConvFn, GraphConvStackFn, edge_conv, graph_conv_stack  # noqa: F401
+from .graph import (EdgeConvFn, GraphAttentionStackFn, GraphConvStackFn, edge_conv, graph_attention_stack,  # noqa: F401
+                    graph_conv_stack)
 from .loss import H1Loss1dFn, H1Loss2dFn, weighted_l2_terms_1d, weighted_l2_terms_2d  # noqa: F401
 from .resize import (ResizeFn, ResizeSegFn, UpsampleFcFn, bilinear_resize, bilinear_resize_seg, out_size,  # noqa: F401
                      upsample_fc)

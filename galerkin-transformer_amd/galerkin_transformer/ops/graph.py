@@ -1,11 +1,12 @@
 """The graph-convolution stack of the GCN feature extractor (reference: GraphConvolution, layers.py:153-198; the layer
-loop of GCN.forward, model.py:409-427) as one autograd operator over all its layers."""
+loop of GCN.forward, model.py:409-427) and the graph-attention stack of the GAT one (GraphAttention, layers.py:201-257;
+GAT.forward, model.py:453-469), each as one autograd operator over all its layers."""
 import torch
 import torch.nn.functional as F
 from torch.autograd import Function
 
 from .. import _hip as H
-from .elementwise import _c
+from .elementwise import _c, _next_salt
 
 MAX_LAYERS = H.GRAPHCONV_MAX_PAIRS
 
@@ -152,3 +153,119 @@ def graph_conv_stack(x, edges, weights, biases, relu):
         if tuple(w.shape) != ((K0 if l == 0 else Cc), Cc) or (biases[l] is not None and tuple(biases[l].shape) != (Cc,)):
             raise ValueError(f"graph_conv_stack: layer {l} weight {tuple(w.shape)}")
     return GraphConvStackFn.apply(x, len(edges), relu, *edges, *weights, *biases)
+
+
+class GraphAttentionStackFn(Function):
+    """x_0 = x;  h_l = x_l W_l;  s_l = h_l a_l[:F];  t_l = h_l a_l[F:];
+    P_l = softmax_j(LeakyReLU(s_i + t_j) where keep_ij, else -9e15);  U_l = dropout(P_l) h_l;  x_{l+1} = relu_l?(ELU?(U_l)).
+
+    The keep bits of adj are packed once (gt_graphattn_mask) and shared by all layers and both directions; no pass forms an
+    n x n float tensor.  Forward, per layer: h on gt_gemm, (s, t) as one [T, 2] product on gt_gemm, gt_graphattn_fwd.  The two
+    thin products around `a` run in the f32 arithmetic whatever the precision mode: the scores feed an exponential, and
+    da = [ds dt]^T h sums a gradient that cancels row by row (sum_j P_ij (dP_ij - D_i) = 0).  Saved
+    per layer: x_l, h_l, (s, t)_l, U_l and the row statistics L_l; the dropout mask is regenerated from (seed, salt).
+    Backward, from the last layer down: gt_graphattn_bwd_row (dU, ds, the partial sums of dt), gt_graphattn_bwd_col (dt and
+    dH with ds a1^T + dt a2^T added), then da = [ds dt]^T h, dW = x^T dH and dx = dH W^T on gt_gemm.  adj gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, adj, relu, cfg, *tensors):
+        L = len(relu)
+        alpha, concat, graph_lap, thresh, p = cfg
+        H.need_f32_cuda(x, adj, *tensors)
+        B, n, K0 = x.shape
+        Fd = tensors[0].shape[1]
+        T = B * n
+        ws = tuple(_c(w) for w in tensors[:L])
+        avs = tuple(_c(a).reshape(2, Fd) for a in tensors[L:])
+        dev = x.device
+        save = any(ctx.needs_input_grad)
+        bits, bitsT, w0 = H.graphattn_mask(adj, graph_lap, thresh)      # (dense, or a channel of an edge tensor in place)
+        salts = tuple(_next_salt(1) if p > 0 else 0 for _ in range(L))
+        xin = _c(x).reshape(T, K0)
+        kept = []
+        for l in range(L):
+            K = ws[l].shape[0]
+            h = torch.empty(T, Fd, dtype=torch.float32, device=dev)
+            H.gemm(xin, ws[l], h, T, Fd, K, layout_b=1, lda=K, ldb=Fd, ldc=Fd)
+            st = torch.empty(T, 2, dtype=torch.float32, device=dev)
+            H.gemm(h, avs[l], st, T, 2, Fd, lda=Fd, ldb=Fd, ldc=2, precision="f32")
+            U = torch.empty(T, Fd, dtype=torch.float32, device=dev) if save else None
+            out = torch.empty(T, Fd, dtype=torch.float32, device=dev)
+            Lg = torch.empty(B, n, dtype=torch.float32, device=dev)
+            H.graphattn_fwd(bits, w0, st, st[:, 1], 2, h, U, out, Lg, B, n, Fd, alpha, concat, relu[l],
+                            H.dropout_desc(p, salts[l], dev))
+            if save:
+                kept += [xin, h, st, U, Lg]
+            xin = out
+        if save:
+            ctx.save_for_backward(bits, bitsT, w0, *ws, *avs, *kept)
+        ctx.cfg = (tuple(relu), alpha, concat, p, salts, B, n, Fd)
+        return xin.reshape(B, n, Fd)
+
+    @staticmethod
+    def backward(ctx, gy):
+        relu, alpha, concat, p, salts, B, n, Fd = ctx.cfg
+        L = len(relu)
+        sv = ctx.saved_tensors
+        bits, bitsT, w0 = sv[:3]
+        ws, avs, kept = sv[3:3 + L], sv[3 + L:3 + 2 * L], sv[3 + 2 * L:]
+        need = ctx.needs_input_grad
+        need_w, need_a = need[4:4 + L], need[4 + L:]
+        dev, T = gy.device, B * n
+        G = _c(gy).reshape(T, Fd)
+        dws, das, dx = [None] * L, [None] * L, None
+        for l in range(L - 1, -1, -1):
+            xin, h, st, U, Lg = kept[5 * l:5 * l + 5]
+            drop = H.dropout_desc(p, salts[l], dev)
+            dU = torch.empty(T, Fd, dtype=torch.float32, device=dev)
+            dst = torch.empty(T, 2, dtype=torch.float32, device=dev)
+            dtp = torch.empty(B, H.graphattn_words(n), n, dtype=torch.float32, device=dev)
+            H.graphattn_bwd_row(bits, st, st[:, 1], 2, Lg, G, U, h, dU, dst, dtp, B, n, Fd, alpha, concat, relu[l], drop)
+            dH = torch.empty(T, Fd, dtype=torch.float32, device=dev)
+            H.graphattn_bwd_col(bitsT, w0, st, st[:, 1], 2, Lg, dU, avs[l], dst, dtp, dst[:, 1], dH, B, n, Fd, alpha, drop)
+            K = ws[l].shape[0]
+            if need_a[l]:
+                da = torch.empty(2, Fd, dtype=torch.float32, device=dev)
+                H.gemm(dst, h, da, 2, Fd, T, layout_a=1, layout_b=1, lda=2, ldb=Fd, ldc=Fd, split_k=0, precision="f32")
+                das[l] = da.reshape(2 * Fd, 1)
+            if need_w[l]:
+                dws[l] = torch.empty(K, Fd, dtype=torch.float32, device=dev)
+                H.gemm(xin, dH, dws[l], K, Fd, T, layout_a=1, layout_b=1, lda=K, ldb=Fd, ldc=Fd, split_k=0)
+            if l > 0 or need[0]:
+                G = torch.empty(T, K, dtype=torch.float32, device=dev)
+                H.gemm(dH, ws[l], G, T, K, Fd, lda=Fd, ldb=Fd, ldc=K)
+                if l == 0:
+                    dx = G.reshape(B, n, K)
+        return (dx, None, None, None, *dws, *das)
+
+
+def graph_attention_stack(x, adj, Ws, as_, relu, *, alpha=1e-2, concat=True, graph_lap=True, thresh=1e-6, p=0.0):
+    """x [B, n, in] -> [B, n, F] through len(Ws) graph-attention layers that share adj [B, n, n].
+
+    Ws[l]: [in_l, F] (in_0 = in, then F); as_[l]: [2F, 1]; relu[l]: a ReLU behind layer l's ELU; concat: the ELU itself;
+    graph_lap / thresh: keep |adj| > thresh, else adj > 0; p: the dropout of the attention weights (0: none)."""
+    Ws, as_, relu = tuple(Ws), tuple(as_), tuple(bool(r) for r in relu)
+    L = len(Ws)
+    if L < 1 or len(as_) != L or len(relu) != L:
+        raise ValueError("graph_attention_stack: one W, one a and one ReLU flag per layer")
+    if x.dim() != 3 or adj.dim() != 3:
+        raise ValueError(f"graph_attention_stack: x is {tuple(x.shape)}, adj {tuple(adj.shape)}; wanted [B, n, in], [B, n, n]")
+    B, n, K0 = x.shape
+    Fd = Ws[0].shape[1]
+    if tuple(adj.shape) != (B, n, n) or B < 1 or n < 1:
+        raise ValueError(f"graph_attention_stack: adj {tuple(adj.shape)} against x {tuple(x.shape)}")
+    for l, (w, a) in enumerate(zip(Ws, as_)):
+        if tuple(w.shape) != ((K0 if l == 0 else Fd), Fd) or tuple(a.shape) != (2 * Fd, 1):
+            raise ValueError(f"graph_attention_stack: layer {l} W {tuple(w.shape)}, a {tuple(a.shape)}")
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"graph_attention_stack: dropout p = {p}")
+    if Fd % 4 or Fd > H.GRAPHATTN_MAX_F:
+        raise H.GtNotSupported(f"graph_attention_stack: F = {Fd}; the gt_graphattn_* kernels take F % 4 == 0, F <= "
+                               f"{H.GRAPHATTN_MAX_F}")
+    if n > H.GRAPHATTN_MAX_N:
+        raise H.GtNotSupported(f"graph_attention_stack: n = {n} > {H.GRAPHATTN_MAX_N}")
+    if alpha < 0:
+        raise H.GtNotSupported("graph_attention_stack: a negative LeakyReLU slope")
+    H.need_f32_cuda(x, adj, *Ws, *as_)
+    return GraphAttentionStackFn.apply(x, adj, relu, (float(alpha), bool(concat), bool(graph_lap), float(thresh), float(p)),
+                                       *Ws, *as_)

@@ -960,6 +960,51 @@ int gt_graphconv_bwd_data(const gt_edge_groups* E, const float* G, int64_t ldg, 
 int gt_graphconv_bwd_edge(const gt_edge_groups* dE, const gt_graph_pairs* pairs, int64_t ldg, int64_t lds, int32_t B, int32_t n, int32_t C,
                           void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fused masked graph attention: the reference's GraphAttention (layers.py:201-257) and its autograd backward, for the GAT
+ * feature extractor (model.py:430-469).  ABI v21, additive.  With h = node W [B, n, F], s = h a[:F], t = h a[F:] (the caller's
+ * products; s and t are read at (b n + i) ldst, so an interleaved [B n, 2] pair is ldst = 2):
+ *     keep_ij = graph_lap ? |adj_ij| > thresh : adj_ij > 0                                   (strict)
+ *     e_ij    = LeakyReLU_alpha(s_i + t_j) where keep_ij, else the reference's literal -9e15
+ *     P       = softmax_j(e):  P_ij = keep_ij ? exp(e_ij - L_i) : w0_i,   L_i = logsumexp_{j kept} e_ij
+ *               (a row that keeps nothing: every weight is 1/n; then w0_i = 1/n and L_i = log n; every other row: w0_i = 0)
+ *     Pm_ij   = P_ij m_ij,  m_ij = 0 or 1/(1-p): ONE keep decision per (seed, salt, b, i, j), shared by all entry points
+ *     U       = Pm h;   out = relu?(concat ? ELU(U) : U)
+ *   gt_graphattn_mask      adj [B, n, n] with adj_ij at ((b n + i) n + j) adj_stride (1: dense; E: channel 0 of an edge tensor
+ *                          [B, n, n, E], read in place) -> bits, bitsT: [B, n, ceil(n/64)] 64-bit words, bit (j mod 64) of word (b, i, j / 64)
+ *                          = keep_ij and bit (i mod 64) of word (b, j, i / 64) = keep_ij, padding bits 0; w0 [B, n].  Once per
+ *                          layer stack: adj is read only here, in row order.
+ *   gt_graphattn_fwd       L [B, n], then U (may be NULL: not stored) and out, leading dimension ldo.
+ *   gt_graphattn_bwd_row   dU = dout * act'(U) [B, n, lddu] (written), ds_i = sum_j dz_ij (at (b n + i) ldst) with
+ *                          dz_ij = P_ij (m_ij dU_i.h_j - dU_i.U_i) LeakyReLU'(s_i + t_j) keep_ij, and the partial column sums
+ *                          dt_part[b, r, j] = sum over the rows i of the 64-row tile r of dz_ij: [B, ceil(n/64), n] floats.
+ *                          dout and U share the leading dimension ldo.
+ *   gt_graphattn_bwd_col   dt_j = sum_r dt_part[b, r, j] (in tile order, written at (b n + j) ldst) and
+ *                          dH_j = sum_i Pm_ij dU_i + ds_j a[:F]^T + dt_j a[F:]^T, over the transposed bits; a is [2F].
+ *   gt_graphattn_weights   Pm [B, n, n] dense, for a caller who wants the attention weights.
+ * fp32 arithmetic whatever the GEMM precision mode, v_mfma_f32_16x16x4_f32 for the products, no atomics, fixed summation
+ * orders: bit-identical from run to run.  The caller's stream, no allocation.  B, n, F < 1, ldst < 1, a leading dimension
+ * < F, a NULL tensor, adj_stride < 1, a dropout p >= 1 or without a seed: GT_EINVAL.  F % 4 != 0, F > GT_GRAPHATTN_MAX_F,
+ * n > GT_GRAPHATTN_MAX_N, B > 65535, alpha < 0 (fwd): GT_ENOTSUP.  Decided from the arguments alone, nothing launched.
+ * ------------------------------------------------------------------------------------------- */
+#define GT_GRAPHATTN_MAX_N 8192
+#define GT_GRAPHATTN_MAX_F 256
+int gt_graphattn_mask(const float* adj, int64_t adj_stride, void* bits, void* bitsT, float* w0, int32_t B, int32_t n,
+                      int32_t graph_lap, float thresh, void* stream);
+int gt_graphattn_fwd(const void* bits, const float* w0, const float* s, const float* t, int64_t ldst, const float* h,
+                     int64_t ldh, float* U, float* out, int64_t ldo, float* L, int32_t B, int32_t n, int32_t F,
+                     float alpha, int32_t concat, int32_t relu, const gt_dropout* drop, void* stream);
+int gt_graphattn_bwd_row(const void* bits, const float* s, const float* t, int64_t ldst, const float* L,
+                         const float* dout, const float* U, int64_t ldo, const float* h, int64_t ldh, float* dU,
+                         int64_t lddu, float* ds, float* dt_part, int32_t B, int32_t n, int32_t F, float alpha,
+                         int32_t concat, int32_t relu, const gt_dropout* drop, void* stream);
+int gt_graphattn_bwd_col(const void* bitsT, const float* w0, const float* s, const float* t, int64_t ldst,
+                         const float* L, const float* dU, int64_t lddu, const float* a, const float* ds,
+                         const float* dt_part, float* dt, float* dH, int64_t lddh, int32_t B, int32_t n, int32_t F,
+                         float alpha, const gt_dropout* drop, void* stream);
+int gt_graphattn_weights(const void* bits, const float* w0, const float* s, const float* t, int64_t ldst, const float* L,
+                         float* Pm, int32_t B, int32_t n, float alpha, const gt_dropout* drop, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -467,27 +467,38 @@ def test_bilinear_resize_autograd_scale_factor(H, gpu_device):
 def test_gemm_width_remainder_split(H, gpu_device, N, lb):
     """Widths just above a multiple of 128 run as two launches (aligned part + narrow remainder): every
     epilogue term (bias, rank update, add, pre, aux, dropout index, residual) must follow the column
-    offset.  144 = h*(d_k+p) of the Darcy model."""
+    offset.  144 = h*(d_k+p) of the Darcy model.  The library splits only when the aligned part alone fills
+    the chip (>= 512 tiles of 128 rows): M = 333 is the one-launch form of the same call, M = 65536 + 37 the
+    split one -- asserted from gt_gemm_plan, so that the second shape cannot quietly stop splitting."""
+    import ctypes as C
     dev = gpu_device
-    H.set_seed(4321, dev)
-    M, K, p = 333, 136, 2
-    A = rnd(M, K, dev=dev, seed=30)
-    Bm = rnd(N, K + p, dev=dev, seed=31, scale=0.3) if lb == 0 else rnd(K, N, dev=dev, seed=31, scale=0.3)
-    bias, ea = rnd(N, dev=dev, seed=32), rnd(M, p, dev=dev, seed=33)
-    eb = rnd(N, p, dev=dev, seed=34)
-    add, aux, res = rnd(M, N, dev=dev, seed=35), rnd(M, N, dev=dev, seed=36), rnd(M, N, dev=dev, seed=37)
-    d = H.dropout_desc(0.25, salt=5, device=dev)
-    mask = H.dropout_apply(torch.ones(M * N, device=dev), d).reshape(M, N).double()
-    Cc, pre = torch.empty(M, N, device=dev), torch.empty(M, N, device=dev)
-    H.gemm(A, Bm, Cc, M, N, K, layout_b=lb, lda=K, ldb=(K + p if lb == 0 else N), ldc=N, bias=bias, rp=p, rp_a=ea,
-           rp_lda=p, rp_b=eb, rp_ldb=p, add=add, ldadd=N, pre=pre, ldpre=N, act=H.ACT_SILU, aux_op=H.AUX_MUL,
-           aux=aux, ldaux=N, aux_scale=0.5, drop=d, res=res, ldr=N, out_scale=-1.0)
-    torch.cuda.synchronize()
-    Bk = Bm[:, :K].double().t() if lb == 0 else Bm.double()
-    p64 = A.double() @ Bk + bias.double() + ea.double() @ eb.double().t() + add.double()
-    assert rel_l2(pre, p64) < KTOL
-    ref = res.double() - torch.nn.functional.silu(p64) * aux.double() * 0.5 * mask
-    assert rel_l2(Cc, ref) < KTOL
+    for M in (333, 65536 + 37):
+        H.set_seed(4321, dev)
+        K, p = 136, 2
+        dsc = H._new_desc()
+        prec = None if M == 333 else "f16x2"     # (the suite's default mode; named so that the split does not hang on it)
+        dsc.M, dsc.N, dsc.K, dsc.layout_b, dsc.precision = M, N, K, lb, H.PREC_CODE[prec or H.get_precision()]
+        bm, bn = C.c_int32(), C.c_int32()
+        H.check(H.lib().gt_gemm_plan(C.byref(dsc), C.byref(bm), C.byref(bn), None), "gt_gemm_plan")
+        splits = bn.value == 128 and -(-M // bm.value) * (N // 128) >= 512
+        assert splits == (M > 333), (M, bm.value, bn.value)
+        A = rnd(M, K, dev=dev, seed=30)
+        Bm = rnd(N, K + p, dev=dev, seed=31, scale=0.3) if lb == 0 else rnd(K, N, dev=dev, seed=31, scale=0.3)
+        bias, ea = rnd(N, dev=dev, seed=32), rnd(M, p, dev=dev, seed=33)
+        eb = rnd(N, p, dev=dev, seed=34)
+        add, aux, res = rnd(M, N, dev=dev, seed=35), rnd(M, N, dev=dev, seed=36), rnd(M, N, dev=dev, seed=37)
+        d = H.dropout_desc(0.25, salt=5, device=dev)
+        mask = H.dropout_apply(torch.ones(M * N, device=dev), d).reshape(M, N).double()
+        Cc, pre = torch.empty(M, N, device=dev), torch.empty(M, N, device=dev)
+        H.gemm(A, Bm, Cc, M, N, K, layout_b=lb, lda=K, ldb=(K + p if lb == 0 else N), ldc=N, bias=bias, rp=p, rp_a=ea,
+               rp_lda=p, rp_b=eb, rp_ldb=p, add=add, ldadd=N, pre=pre, ldpre=N, act=H.ACT_SILU, aux_op=H.AUX_MUL,
+               aux=aux, ldaux=N, aux_scale=0.5, drop=d, res=res, ldr=N, out_scale=-1.0, precision=prec)
+        torch.cuda.synchronize()
+        Bk = Bm[:, :K].double().t() if lb == 0 else Bm.double()
+        p64 = A.double() @ Bk + bias.double() + ea.double() @ eb.double().t() + add.double()
+        assert rel_l2(pre, p64) < KTOL
+        ref = res.double() - torch.nn.functional.silu(p64) * aux.double() * 0.5 * mask
+        assert rel_l2(Cc, ref) < KTOL
 
 
 @pytest.mark.parametrize("split,batch,p_drop,sign", [(1, 1, 0.0, 1.0), (0, 1, 0.0, -1.0), (7, 1, 0.3, -1.0),

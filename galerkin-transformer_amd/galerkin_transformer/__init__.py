@@ -5,11 +5,12 @@ the encoder layer and the spectral decoder execute in ``_lib/libgt_hip.so`` (han
 gfx950, C ABI in include/gt_hip.h).  There is no CPU fallback for those operators.
 """
 from .layers import *          # noqa: F401,F403
-from .layers import (EdgeEncoder, FeedForward, GraphAttention, GraphConvolution, Identity, SimpleAttention, SpectralConv1d, SpectralConv2d,  # noqa: F401
+from .layers import (EdgeEncoder, FeedForward, GraphAttention, GraphConvolution, Identity, Favor, RandomFourierAttention, RandomFourierFeatures, SimpleAttention, SpectralConv1d, SpectralConv2d,  # noqa: F401
                      get_attention_dropout, push_attention_masks, set_attention_dropout)
 from .model import *           # noqa: F401,F403
 from .model import (GAT, GCN, FourierTransformer, FourierTransformer2D, FourierTransformer2DLite,  # noqa: F401
-                    FourierTransformerEncoderLayer, PointwiseRegressor, SimpleTransformer,
+                    FourierTransformerEncoderLayer, PointwiseRegressor, RandomFeatureEncoderLayer,
+                    RandomFeatureTransformer, SimpleTransformer,
                     SimpleTransformerEncoderLayer, SpectralRegressor)
 
 from .ft import (BurgersDataset, DarcyDataset, UnitGaussianNormalizer, WeightedL2Loss,  # noqa: F401

@@ -163,6 +163,15 @@ _PROTOS = {
                                                          C.c_void_p]),
     "gt_row_softmax_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(GtDropout),
                                                          C.c_void_p]),
+    "gt_rfattn_slabs": (C.c_int32, [C.c_int32]),
+    "gt_rfattn_ws_bytes": (C.c_int64, [C.c_int32] * 3),
+    "gt_rfattn_kv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 +
+                     [C.c_void_p, C.c_int64, C.c_void_p]),
+    "gt_rfattn_q": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_float, C.c_void_p]),
+    "gt_rfattn_bwd_q": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p] + [C.c_int32] * 4 +
+                        [C.c_void_p, C.c_int64, C.c_void_p]),
+    "gt_rfattn_bwd_kv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_int32] * 4 +
+                         [C.c_void_p]),
     "gt_dropact_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(GtDropout), C.c_int32, C.POINTER(GtDropout),
                                  C.c_int32, C.c_void_p]),
     "gt_dropact_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(GtDropout), C.c_int32,
@@ -1790,6 +1799,68 @@ def row_softmax_bwd(P, dPm, rows: int, n: int, mask, drop, dS=None, row0: int = 
 
 
 # ----------------------------------------------------------------------------------- 2-D training objective
+# ----------------------------------------------------------------------------------- random-feature attention (gt_rfattn.hip)
+RFATTN_D = (32, 64, 96)                    # widths of the one head (= number of features m)
+RFATTN_KIND = {"rfa": 0, "favor": 1}       # GT_RFATTN_RFA / GT_RFATTN_FAVOR
+
+
+def rfattn_check(d: int, kind: str):
+    """The refusals of the random-feature kernels, raised before anything is allocated or launched."""
+    if kind not in RFATTN_KIND:
+        raise ValueError(f"random-feature attention: kind must be 'rfa' or 'favor', got {kind!r}")
+    if d not in RFATTN_D:
+        raise GtNotSupported(f"random-feature attention: width d={d} has no kernel (supported: {RFATTN_D})")
+
+
+def rfattn_slabs(n: int) -> int:
+    """Slabs per sample that gt_rfattn_kv / gt_rfattn_bwd_q write for n tokens (merged in a fixed order)."""
+    return int(lib().gt_rfattn_slabs(n))
+
+
+def _rfattn_ws(t: torch.Tensor, B: int, n: int, d: int) -> torch.Tensor:
+    return workspace(t.device, max(16, lib().gt_rfattn_ws_bytes(B, n, d)))
+
+
+def rfattn_kv(K, V, ld: int, omega, B: int, n: int, d: int, kind: str, KVa=None):
+    """gt_rfattn_kv: KVa [B, d, d + 4] = phi(K)^T [V, 1, 0, 0, 0] from the column blocks K, V of a [B*n, ld] matrix."""
+    rfattn_check(d, kind)
+    need_f32_cuda(K, V, omega, KVa)
+    if KVa is None:
+        KVa = torch.empty(B, d, d + 4, dtype=torch.float32, device=K.device)
+    _launch("gt_rfattn_kv", K, V, ld, omega, KVa, B, n, d, RFATTN_KIND[kind], ws=_rfattn_ws(K, B, n, d),
+            flops=2.0 * B * n * d * (d // 2 + d + 4), nbytes=8.0 * B * n * d, shape=(B, n, d))
+    return KVa
+
+
+def rfattn_q(Q, ld: int, omega, KVa, B: int, n: int, d: int, kind: str, eps: float, out=None, den=None):
+    """gt_rfattn_q: (out [B*n, d], den [B*n]) = (phi(Q) KVa[:, :d] / den, phi(Q) . KVa[:, d] + eps)."""
+    rfattn_check(d, kind)
+    need_f32_cuda(Q, omega, KVa, out, den)
+    if out is None:
+        out = torch.empty(B * n, d, dtype=torch.float32, device=Q.device)
+    if den is None:
+        den = torch.empty(B * n, dtype=torch.float32, device=Q.device)
+    _launch("gt_rfattn_q", Q, ld, omega, KVa, out, den, B, n, d, RFATTN_KIND[kind], float(eps),
+            flops=2.0 * B * n * d * (d // 2 + d + 1), nbytes=8.0 * B * n * d, shape=(B, n, d))
+    return out, den
+
+
+def rfattn_bwd(Q, K, V, ld: int, omega, KVa, dOut, out, den, dQ, dK, dV, ldg: int, B: int, n: int, d: int, kind: str,
+               dKVa=None):
+    """gt_rfattn_bwd_q, then gt_rfattn_bwd_kv (which reads the dKVa of the first): dQ, dK, dV into column blocks of a
+    [B*n, ldg] matrix; returns dKVa [B, d, d + 4]."""
+    rfattn_check(d, kind)
+    need_f32_cuda(Q, K, V, omega, KVa, dOut, out, den, dQ, dK, dV, dKVa)
+    if dKVa is None:
+        dKVa = torch.empty(B, d, d + 4, dtype=torch.float32, device=Q.device)
+    k = RFATTN_KIND[kind]
+    _launch("gt_rfattn_bwd_q", Q, ld, omega, KVa, dOut, out, den, dQ, ldg, dKVa, B, n, d, k, ws=_rfattn_ws(Q, B, n, d),
+            flops=2.0 * B * n * d * (4 * d + 8), nbytes=16.0 * B * n * d, shape=(B, n, d))
+    _launch("gt_rfattn_bwd_kv", K, V, ld, omega, dKVa, dK, dV, ldg, B, n, d, k,
+            flops=2.0 * B * n * d * (3 * d + 4), nbytes=16.0 * B * n * d, shape=(B, n, d))
+    return dKVa
+
+
 def h1loss2d_pitch(P: torch.Tensor) -> Optional[int]:
     """Pixel pitch (in floats) of an [N, n, n] tensor whose pixels are evenly spaced in memory -- a contiguous tensor (1) or
     channel 0 of a contiguous [N, n, n, c] one (c); None for any other strides."""

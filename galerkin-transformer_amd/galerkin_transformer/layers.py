@@ -824,3 +824,146 @@ class SpectralConv2d(nn.Module):
             y, ft = y if self.return_freq else (y, None)
         y = y.reshape(B, n * n, self.out_dim) if flat else y
         return (y, ft) if self.return_freq else y
+
+
+# --------------------------------------------------------------------------------------- random-feature attention (HIP)
+def _orthogonal_random_matrix(rows: int, columns: int, device, generator=None) -> torch.Tensor:
+    """[rows, columns] in blocks of ``rows`` columns: each block is the Q factor of a Gaussian [rows, rows] matrix with
+    column c scaled by the norm of the Gaussian's row c (norms distributed like those of N(0, I) vectors).  The QR runs on
+    ``device`` when its solver library is available, else on the host."""
+    w = torch.zeros(rows, columns, device=device)
+    for start in range(0, columns, rows):
+        end = min(start + rows, columns)
+        block = torch.randn(rows, rows, device=device, generator=generator)
+        norms = block.pow(2).sum(1).sqrt()
+        try:
+            q, _ = torch.linalg.qr(block)
+        except RuntimeError:                 # no device QR in this build: the draw is plumbing, the host does it
+            q = torch.linalg.qr(block.cpu())[0].to(device)
+        w[:, start:end] = q[:, :end - start] * norms[None, :end - start]
+    return w
+
+
+class RandomFourierFeatures(nn.Module):
+    """phi(x) = sqrt(2 / n_dims) [cos u, sin u], u = (x d^(-1/4)) omega: random Fourier features of the Gaussian kernel
+    (reference examples/ex1_burgers_random_fourier_features.py:84-148), ``omega`` [query_dimensions, n_dims // 2] a buffer.
+
+    ``new_feature_map`` redraws ``omega`` (standard normal; block-orthogonal with ``orthogonal=True``) unless
+    ``deterministic_eval`` is set in eval mode, as the reference does, or the attribute ``redraw`` is False (tests, captured
+    training steps).  The Gaussian redraw can be part of a captured graph; the orthogonal one (a QR) cannot.  The attention
+    modules never call ``forward``: the fused kernels evaluate phi in registers; it is the definition in torch, for
+    comparisons."""
+    kind = "rfa"
+
+    def __init__(self, query_dimensions, n_dims=None, orthogonal=False, deterministic_eval=False):
+        super().__init__()
+        self.n_dims = n_dims or query_dimensions
+        self.query_dims = self.query_dimensions = query_dimensions
+        self.orthogonal = orthogonal
+        self.softmax_temp = 1 / math.sqrt(query_dimensions)
+        self.deterministic_eval = deterministic_eval
+        self.redraw = True
+        self.register_buffer("omega", torch.zeros(self.query_dimensions, self.n_dims // 2))
+
+    @classmethod
+    def factory(cls, *args, **kwargs):
+        def inner(query_dims):
+            return cls(query_dims, *args, **kwargs)
+        return inner
+
+    def new_feature_map(self, device):
+        if (self.deterministic_eval and not self.training) or not self.redraw:
+            return
+        rows, cols = self.query_dimensions, self.n_dims // 2
+        if self.orthogonal:
+            self.omega = _orthogonal_random_matrix(rows, cols, device)
+        else:
+            self.omega = torch.randn(rows, cols, device=device)
+
+    def _u(self, x):
+        return (x * math.sqrt(self.softmax_temp)) @ self.omega
+
+    def forward(self, x):
+        u = self._u(x)
+        return torch.cat([torch.cos(u), torch.sin(u)], dim=-1) * math.sqrt(2 / self.n_dims)
+
+
+class Favor(RandomFourierFeatures):
+    """phi(x) = [exp(u - c), exp(-u - c)], c = |x d^(-1/4)|^2 / 2 + log(n_dims) / 2: the positive orthogonal random features
+    of the Performer (reference example :151-205)."""
+    kind = "favor"
+
+    def __init__(self, query_dimensions, n_dims=None, orthogonal=True, deterministic_eval=False):
+        super().__init__(query_dimensions, n_dims=n_dims, orthogonal=orthogonal, deterministic_eval=deterministic_eval)
+
+    def forward(self, x):
+        u = self._u(x)
+        c = 0.5 * self.softmax_temp * x.pow(2).sum(-1, keepdim=True) + 0.5 * math.log(self.n_dims)
+        return torch.cat([torch.exp(u - c), torch.exp(-u - c)], dim=-1)
+
+
+class RandomFourierAttention(nn.Module):
+    """Linear-complexity attention through a random feature map (reference example :208-318), ONE head:
+    out_projection([phi(Q) (phi(K)^T V) / (phi(Q) . sum phi(K) + eps), pos]) on the gt_rfattn_* kernels
+    (ops.random_feature_attention).  ``attention_type``: 'favor' (Performer) or 'rfa'.
+
+    The reference builds its feature map for d_model inputs and applies it to d_model / n_heads wide heads, so it only runs
+    with n_heads == 1: any other value is a ValueError here.  d_model outside (32, 64, 96) has no kernel
+    (NotImplementedError), ``pos`` is required (ValueError), and query, key and value must be one tensor.  ``omega`` is redrawn
+    at every forward (see RandomFourierFeatures; ``redraw = False`` on this module freezes it)."""
+
+    def __init__(self, d_model, n_heads, pos_dim=1, eps=1e-6, attention_type='favor', xavier_init=1.0, diagonal_weight=0.0):
+        super().__init__()
+        if n_heads != 1:
+            raise ValueError(f"RandomFourierAttention: n_heads={n_heads}: the feature map is built for d_model inputs, so the "
+                             "attention is defined for one head only (n_heads=1)")
+        H.rfattn_check(d_model, attention_type)
+        f = Favor if attention_type == 'favor' else RandomFourierFeatures
+        self.feature_map = f(d_model, n_dims=d_model)
+        self.query_projection = nn.Linear(d_model, d_model)
+        self.key_projection = nn.Linear(d_model, d_model)
+        self.value_projection = nn.Linear(d_model, d_model)
+        self.out_projection = nn.Linear(d_model + pos_dim, d_model)
+        self.n_heads = n_heads
+        self.eps = eps
+        self.attention_type = attention_type
+        self.xavier_init = xavier_init
+        self.diagonal_weight = diagonal_weight
+        for layer in [self.query_projection, self.key_projection, self.value_projection]:
+            self._reset_parameters(layer)
+
+    def _reset_parameters(self, layer):
+        for param in layer.parameters():
+            if param.ndim > 1:
+                xavier_uniform_(param, gain=self.xavier_init)
+                if self.diagonal_weight > 0.0:
+                    param.data += self.diagonal_weight * torch.diag(torch.ones(param.size(-1), dtype=torch.float))
+            else:
+                constant_(param, 0)
+
+    @property
+    def redraw(self) -> bool:
+        return self.feature_map.redraw
+
+    @redraw.setter
+    def redraw(self, flag: bool):
+        self.feature_map.redraw = bool(flag)
+
+    def fused_forward(self, x, pos, residual=None, p_out=0.0):
+        if pos is None:
+            raise ValueError("RandomFourierAttention: `pos` is required (it is concatenated in front of the output "
+                             "projection unconditionally)")
+        self.feature_map.new_feature_map(x.device)
+        q, k, v = self.query_projection, self.key_projection, self.value_projection
+        wqkv = ops.packed_params([q.weight, k.weight, v.weight])
+        bqkv = ops.packed_params([q.bias, k.bias, v.bias])
+        return ops.random_feature_attention(x, pos, wqkv, bqkv, self.feature_map.omega, self.out_projection.weight,
+                                            self.out_projection.bias, kind=self.feature_map.kind, eps=self.eps,
+                                            res=residual, p_out=p_out)
+
+    def forward(self, queries, keys=None, values=None, pos=None):
+        keys = queries if keys is None else keys
+        values = keys if values is None else values
+        if keys is not queries or values is not queries:
+            raise NotImplementedError("RandomFourierAttention: queries, keys and values must be one tensor (self-attention)")
+        return self.fused_forward(queries, pos)

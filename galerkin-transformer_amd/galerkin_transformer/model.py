@@ -18,7 +18,7 @@ from torch.nn.init import constant_, xavier_uniform_
 from . import _hip as H
 from . import ops
 from .layers import (Conv2dEncoder, DeConv2dBlock, EdgeEncoder, FeedForward, GraphAttention, GraphConvolution, Identity, Interp2dEncoder,
-                     Interp2dUpsample, PositionalEncoding, SimpleAttention, SpectralConv1d, SpectralConv2d, _act_module,
+                     Interp2dUpsample, PositionalEncoding, RandomFourierAttention, SimpleAttention, SpectralConv1d, SpectralConv2d, _act_module,
                      _act_name, default)
 
 current_path = os.path.dirname(os.path.abspath(__file__))
@@ -627,5 +627,87 @@ class FourierTransformer2DLite(_ConfiguredModel):
             x = encoder(x, pos)
         x = self._drop(x)
         x = x.view(bsz, n_grid, n_grid, -1)
+        x = self.regressor(x, grid=grid)
+        return dict(preds=x, preds_freq=None, preds_latent=None, attn_weights=None)
+
+
+# --------------------------------------------------------------------------------------- random-feature baselines
+class RandomFeatureEncoderLayer(nn.Module):
+    """x <- LN1(x + drop1(attn(x, x, x, pos))); x <- LN2(x + drop2(ff(x))): the post-norm encoder layer of the reference's
+    examples/ex1_burgers_random_fourier_features.py (:321-386) around RandomFourierAttention, always with both LayerNorms.
+    Arguments, defaults and state-dict keys are the example's; ``pos_dim`` is added (the example fixes it at 1)."""
+
+    def __init__(self, d_model=96, n_head=2, dim_feedforward=512, attention_type='favor', layer_norm=True, attn_norm=None,
+                 norm_type='layer', norm_eps=None, xavier_init: float = 1e-2, diagonal_weight: float = 1e-2,
+                 activation_type='relu', dropout=0.1, ffn_dropout=None, debug=False, pos_dim=1):
+        super().__init__()
+        dropout = default(dropout, 0.05)
+        ffn_dropout = default(ffn_dropout, dropout)
+        norm_eps = default(norm_eps, 1e-5)
+        self.attn = RandomFourierAttention(d_model, n_head, pos_dim=pos_dim, attention_type=attention_type,
+                                           xavier_init=xavier_init, diagonal_weight=diagonal_weight)
+        self.d_model = d_model
+        self.n_head = n_head
+        self.norm_eps = norm_eps
+        self.layer_norm1 = nn.LayerNorm(d_model, eps=norm_eps)
+        self.layer_norm2 = nn.LayerNorm(d_model, eps=norm_eps)
+        dim_feedforward = default(dim_feedforward, 2 * d_model)
+        self.ff = FeedForward(in_dim=d_model, dim_feedforward=dim_feedforward, activation=activation_type,
+                              dropout=ffn_dropout)
+        self.dropout1 = nn.Dropout(dropout)
+        self.dropout2 = nn.Dropout(dropout)
+        self.debug = debug
+
+    def forward(self, x, pos=None):
+        p1 = self.dropout1.p if self.training else 0.0
+        p2 = self.dropout2.p if self.training else 0.0
+        x = self.attn.fused_forward(x, pos, residual=x, p_out=p1)
+        x = ops.layer_norm(x, self.layer_norm1.weight, self.layer_norm1.bias, self.norm_eps)
+        x = self.ff.fused_forward(x, residual=x, p_out=p2)
+        return ops.layer_norm(x, self.layer_norm2.weight, self.layer_norm2.bias, self.norm_eps)
+
+
+class RandomFeatureTransformer(_ConfiguredModel):
+    """The model of the reference's random-feature example (its ``SimpleTransformer``, :389-480): cat([node, pos]) ->
+    Identity feature layer -> N RandomFeatureEncoderLayer -> dropout -> SpectralRegressor.  Config keys as in the example:
+    node_feats (coordinates included), pos_dim, n_hidden, n_head (1), num_encoder_layers, dim_feedforward,
+    attention_type ('favor' / 'rfa'), xavier_init, diagonal_weight, encoder_dropout, ffn_dropout, dropout, and the
+    regressor's n_targets, freq_dim, num_regressor_layers, fourier_modes, spacial_dim, spacial_fc, regressor_activation,
+    decoder_dropout."""
+
+    def __init__(self, **kwargs):
+        super().__init__()
+        self._read_config(kwargs)
+        if self.attention_type not in ('favor', 'rfa'):
+            raise ValueError(f"RandomFeatureTransformer: attention_type={self.attention_type!r} (use 'favor' or 'rfa'; the "
+                             "other types are SimpleTransformer's)")
+        self.pos_dim = default(self.pos_dim, 1)
+        self.spacial_dim = default(self.spacial_dim, self.pos_dim)
+        self.spacial_fc = default(self.spacial_fc, False)
+        layer = RandomFeatureEncoderLayer(d_model=self.n_hidden, n_head=self.n_head, dim_feedforward=self.dim_feedforward,
+                                          layer_norm=self.layer_norm, attention_type=self.attention_type,
+                                          attn_norm=self.attn_norm, norm_type=self.norm_type, xavier_init=self.xavier_init,
+                                          diagonal_weight=self.diagonal_weight, dropout=self.encoder_dropout,
+                                          ffn_dropout=self.ffn_dropout, debug=self.debug, pos_dim=self.pos_dim)
+        self.feat_extract = Identity(in_features=self.node_feats, out_features=self.n_hidden)
+        self.encoder_layers = nn.ModuleList([copy.deepcopy(layer) for _ in range(self.num_encoder_layers)])
+        self.regressor = SpectralRegressor(in_dim=self.n_hidden, n_hidden=self.n_hidden, freq_dim=self.freq_dim,
+                                           out_dim=self.n_targets, num_spectral_layers=self.num_regressor_layers,
+                                           modes=self.fourier_modes, spacial_dim=self.spacial_dim,
+                                           spacial_fc=self.spacial_fc, dim_feedforward=self.freq_dim,
+                                           activation=self.regressor_activation, dropout=self.decoder_dropout)
+        self.config = dict(self.config)
+        self.__name__ = self.attention_type.capitalize() + 'Transformer'
+
+    def set_redraw(self, flag: bool):
+        """Freeze (False) or release (True) the per-forward redraw of every layer's ``omega``."""
+        for layer in self.encoder_layers:
+            layer.attn.redraw = flag
+
+    def forward(self, node, edge, pos, grid=None):
+        x = self.feat_extract(torch.cat([node, pos], dim=-1), edge)
+        for encoder in self.encoder_layers:
+            x = encoder(x, pos)
+        x = self._drop(x)
         x = self.regressor(x, grid=grid)
         return dict(preds=x, preds_freq=None, preds_latent=None, attn_weights=None)

@@ -19,6 +19,7 @@ One module per operator family; this file only re-exports (every name is the obj
 ``graph``        the graph-convolution stack of the GCN feature extractor, ``graph_conv_stack``; the edge encoder's
                  library convolution with a reproducible weight gradient, ``edge_conv``
 ``loss``         the weighted-L2 / H1 objectives per sample: ``H1Loss2dFn`` (2-D), ``H1Loss1dFn`` (1-D)
+``rfattn``       random-feature attention ('rfa' / 'favor'): ``RandomFeatureAttentionFn``, ``random_feature_attention``
 ``attention``    the attention-dropout mode and mask queue, ``SimpleAttentionFn`` with its projection stage and cores,
                  ``CrossAttentionFn`` on the same cores
 """
@@ -41,5 +42,6 @@ from .graph import (EdgeConvFn, GraphAttentionStackFn, GraphConvStackFn, edge_co
 from .loss import H1Loss1dFn, H1Loss2dFn, weighted_l2_terms_1d, weighted_l2_terms_2d  # noqa: F401
 from .resize import (ResizeFn, ResizeSegFn, UpsampleFcFn, bilinear_resize, bilinear_resize_seg, out_size,  # noqa: F401
                      upsample_fc)
+from .rfattn import RandomFeatureAttentionFn, random_feature_attention  # noqa: F401
 from .scaler_conv import (AvgPool2ActFn, ConvTranspose3x3S2Fn, avgpool2_act, conv_transpose3x3s2,  # noqa: F401
                           deconv_out_size)

@@ -583,6 +583,41 @@ int gt_row_softmax_bwd(const float* P, const float* dPm, float* dS, int64_t rows
                        const gt_dropout* drop, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Random-feature attention (examples/ex1_burgers_random_fourier_features.py, attention_type 'rfa' / 'favor'; additive, same
+ * ABI): ONE head of width d with m = d features, Om [d][m/2] the random projection, s = d^(-1/4):
+ *     u(z)  = (s z) Om
+ *     rfa   : phi(z) = sqrt(2/m) [cos u, sin u]
+ *     favor : phi(z) = [exp(u - c), exp(-u - c)],  c = |s z|^2 / 2 + log(m) / 2
+ *     KVa   = phi(K)^T [V, 1]                     [B][m][d + 4]: columns < d are KV, column d is sum_tokens phi(K),
+ *                                                  columns d + 1 .. d + 3 are written as zeros
+ *     den   = phi(Q) . KVa[:, d] + eps,   out = phi(Q) KVa[:, :d] / den           (no 1/n, no dropout)
+ * Q, K, V are column blocks of row-major matrices with leading dimension ld (the packed projection [B*n][3d]: ld = 3d);
+ * dQ, dK, dV go to column blocks with leading dimension ldg.  out, dOut [B*n][d] and den [B*n] are dense.  fp32 on
+ * v_mfma_f32_16x16x4_f32 with library exp / sin / cos in every precision mode; phi and u are never written to memory.
+ *     gt_rfattn_kv      -> KVa                                   one slab per 256 tokens and sample, merged in a fixed order
+ *     gt_rfattn_q       -> out, den
+ *     gt_rfattn_bwd_q   -> dQ, dKVa = phi(Q)^T [dOut / den, -(dOut . out) / den]      (slabs as gt_rfattn_kv)
+ *     gt_rfattn_bwd_kv  -> dK, dV from dKVa                      (call it after gt_rfattn_bwd_q)
+ * gt_rfattn_slabs(n): slabs per sample; gt_rfattn_ws_bytes: scratch of gt_rfattn_kv / gt_rfattn_bwd_q, 0 with one slab (ws may
+ * then be NULL).  Tokens at or beyond n leave no trace in KVa, dKVa.  No atomics: bit-identical from run to run.  Plain
+ * pointers, the caller's stream, no allocation.  d in {32, 64, 96}, any n >= 1, B <= 65535, else GT_ENOTSUP; another kind, a
+ * NULL tensor, a non-positive size: GT_EINVAL; a tensor off a 16-byte (den: 4-byte) boundary, ld or ldg < d or not a
+ * multiple of 4: GT_EALIGN; ws too small: GT_EWS.  All decided from the arguments alone, nothing launched. */
+#define GT_RFATTN_RFA   0
+#define GT_RFATTN_FAVOR 1
+int32_t gt_rfattn_slabs(int32_t n);
+int64_t gt_rfattn_ws_bytes(int32_t B, int32_t n, int32_t d);
+int gt_rfattn_kv(const float* K, const float* V, int64_t ld, const float* omega, float* KVa, int32_t B, int32_t n, int32_t d,
+                 int32_t kind, void* ws, int64_t ws_bytes, void* stream);
+int gt_rfattn_q(const float* Q, int64_t ld, const float* omega, const float* KVa, float* out, float* den, int32_t B, int32_t n,
+                int32_t d, int32_t kind, float eps, void* stream);
+int gt_rfattn_bwd_q(const float* Q, int64_t ld, const float* omega, const float* KVa, const float* dOut, const float* out,
+                    const float* den, float* dQ, int64_t ldg, float* dKVa, int32_t B, int32_t n, int32_t d, int32_t kind,
+                    void* ws, int64_t ws_bytes, void* stream);
+int gt_rfattn_bwd_kv(const float* K, const float* V, int64_t ld, const float* omega, const float* dKVa, float* dK, float* dV,
+                     int64_t ldg, int32_t B, int32_t n, int32_t d, int32_t kind, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Truncated-DFT stages along the contiguous grid axis of SpectralConv2d (layers.py:1176 rfft2 and :1187
  * irfft2 restricted to the kept modes; the residual nn.Linear of :1128 / :1196 rides on the synthesis).
  * One batch item = one grid line; all tensors dense fp32:

@@ -23,6 +23,10 @@
 // rows of a tile is 16 in-lane registers plus xor 16 / xor 32 shuffles, and all accumulators of an owner sit in that owner's
 // lanes, so the rescale is one per-lane scalar.
 //
+// Tail-free instances (gt_softmax_attn_nopos_*): head tiles exactly DP = d_k = 16*NF floats wide, for attention without
+// coordinate columns (ops.multihead_attention).  The same kernel with the vector-unit tail (ax1 / ax2) and its store compiled
+// out; everything above holds unchanged.
+//
 // Materialised route (need_weights): gt_row_softmax_fwd / _bwd on a score matrix that gt_gemm wrote.
 #include "gt_common.h"
 #include <algorithm>
@@ -57,18 +61,28 @@ typedef const __attribute__((address_space(1))) void* sm_glb_ptr_t;
 
 __device__ __forceinline__ float sm_exp(float x) { return __builtin_amdgcn_exp2f(x * SM_LOG2E); }
 
-// Head tiles are DP = 16*NF + 4 floats wide; LDS tile image [64][DP], linear in float4 granules (gt_fourier.hip).
+// Blocks per CU of an instance (see the kernel's launch bounds).  A tail-free instance (KS a multiple of 4) takes the bound
+// of the tailed instance one granule wider: it holds the same fragment, score and MFMA accumulator sets, and under those
+// bounds none of them spills (DESIGN 4.14 has the compiler's figures).
+constexpr int sm_blocks(int KS, int PASS) {
+    const int k = KS % 4 == 0 ? KS + 1 : KS;
+    return k >= SM_WIDE_KS ? 1 : PASS == SM_BWDKV ? (k > 5 ? 1 : 2) : (PASS == SM_BWDQ ? (k > 9 ? 1 : 2) : (k > 5 ? 2 : 3));
+}
+
+// Head tiles are DP = 16*NF + 4 floats wide (TAIL), or exactly 16*NF (tail-free: KS a multiple of 4); LDS tile image
+// [64][DP], linear in float4 granules (gt_fourier.hip).
 template <int KS, int PASS, int MODE>
 // Blocks per CU: the widest register budget at which no instance spills (d/dK',V' holds four fragment sets, two score tiles
 // and two accumulator sets: from DP = 36 on it takes the whole file, AGPRs included).  The wide instances stage 68 / 100 KiB
 // of stream tiles per block: at most two blocks fit a CU at DP = 68, one at DP = 100, so they are bounded at one and the
 // allocator is free to use AGPRs in every pass.
-__global__ __launch_bounds__(256, KS >= SM_WIDE_KS ? 1 : PASS == SM_BWDKV ? (KS > 5 ? 1 : 2) : (PASS == SM_BWDQ ? (KS > 9 ? 1 : 2) : (KS > 5 ? 2 : 3)))
+__global__ __launch_bounds__(256, sm_blocks(KS, PASS))
 void softmax_core_kernel(const SoftmaxP p) {
-    constexpr int DP = 4 * KS, NF = (DP - 4) / 16, XC = DP - 4, TILE = SM_TS * DP;
+    constexpr bool TAIL = KS % 4 != 0;             // last 4 columns (coordinates + padding) on the vector unit
+    constexpr int DP = 4 * KS, NF = DP / 16, XC = 16 * NF, TILE = SM_TS * DP;
     constexpr bool TWO = PASS != SM_FWD;           // two score tiles (S and dPm)
     constexpr bool DUAL = PASS == SM_BWDKV;        // two second products
-    static_assert(DP % 16 == 4, "head tile width must be 16*NF + 4");
+    static_assert(DP % 16 == 4 || DP % 16 == 0, "head tile width must be 16*NF + 4 or 16*NF");
     __shared__ __attribute__((aligned(16))) float smem[2][2][TILE];
     __shared__ __attribute__((aligned(16))) float sld[2][3][SM_TS];      // d/dK',V': L, D and Lr of the stream rows
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -153,7 +167,7 @@ void softmax_core_kernel(const SoftmaxP p) {
             acc1[dt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (DUAL) acc2[dt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-        ax1[nt][0] = ax1[nt][1] = ax2[nt][0] = ax2[nt][1] = f32x2{0.f, 0.f};
+        if (TAIL) ax1[nt][0] = ax1[nt][1] = ax2[nt][0] = ax2[nt][1] = f32x2{0.f, 0.f};
     }
     float run_m[2] = {-INFINITY, -INFINITY}, run_l[2] = {0.f, 0.f};      // forward: running maximum and sum per owner
 
@@ -236,8 +250,10 @@ void softmax_core_kernel(const SoftmaxP p) {
                 run_l[nt] = run_l[nt] * alpha + sum;
 #pragma unroll
                 for (int dt = 0; dt < NF; ++dt) acc1[dt][nt] *= alpha;
-                ax1[nt][0] *= alpha;
-                ax1[nt][1] *= alpha;
+                if (TAIL) {
+                    ax1[nt][0] *= alpha;
+                    ax1[nt][1] *= alpha;
+                }
             }
         } else {
             // P = exp(S - L) from the saved row statistic
@@ -306,6 +322,7 @@ void softmax_core_kernel(const SoftmaxP p) {
                             acc2[dt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, sb[mt][nt][s], acc2[dt][nt], 0, 0, 0);
                     }
                 }
+                if (!TAIL) continue;
                 // last 4 columns on the vector unit: this lane's stream row `row`, its owner columns
                 const f32x4 x1 = *reinterpret_cast<const f32x4*>(&u1[row * DP + XC]);
 #pragma unroll
@@ -339,6 +356,14 @@ void softmax_core_kernel(const SoftmaxP p) {
                 *reinterpret_cast<f32x4*>(p.O1 + base + (int64_t)ow * hD + dim) = acc1[dt][nt] * e1;
                 if (DUAL) *reinterpret_cast<f32x4*>(p.O2 + base + (int64_t)ow * hD + dim) = acc2[dt][nt] * p.scale;
             }
+        if (!TAIL) {      // no tail store to ride on: lane kq == 0 writes the forward's row statistic
+            if (PASS == SM_FWD && kq == 0 && ow < p.n) {
+                const float lg = logf(run_l[nt]), lv = run_m[nt] + lg;
+                p.L[zrow + ow] = lv;
+                p.L[p.lplane + zrow + ow] = (run_m[nt] - lv) + lg;
+            }
+            continue;
+        }
         // last 4 columns: sum the four kq partials (lanes j, j+16, j+32, j+48), lane kq == 0 stores
         f32x4 v1 = {ax1[nt][0][0], ax1[nt][0][1], ax1[nt][1][0], ax1[nt][1][1]};
         f32x4 v2 = {ax2[nt][0][0], ax2[nt][0][1], ax2[nt][1][0], ax2[nt][1][1]};
@@ -373,8 +398,10 @@ static void softmax_launch(const SoftmaxP& p, dim3 grid, hipStream_t st) {
 #undef GT_SM
 }
 
-// WIDE selects the instance set of the entry point: DP in {20, 36, 52} (gt_softmax_attn_*) or {68, 100} (gt_softmax_attn_wide_*).
-template <int PASS, bool WIDE>
+// SET selects the instance set of the entry point: DP in {20, 36, 52} (gt_softmax_attn_*), {68, 100} (gt_softmax_attn_wide_*)
+// or the tail-free {16, 32, 48, 64, 96} (gt_softmax_attn_nopos_*).
+enum { SM_NARROW = 0, SM_WIDE = 1, SM_NOPOS = 2 };
+template <int PASS, int SET>
 static int softmax_attn(SoftmaxP p, int32_t B, int32_t DP, const gt_dropout* drop, void* stream) {
     if (!p.F1 || !p.T1 || !p.T2 || !p.O1 || !p.L || B <= 0 || p.n <= 0 || p.h <= 0 || DP <= 0) return GT_EINVAL;
     if (PASS != SM_FWD && (!p.F2 || !p.D)) return GT_EINVAL;
@@ -388,7 +415,16 @@ static int softmax_attn(SoftmaxP p, int32_t B, int32_t DP, const gt_dropout* dro
     p.lplane = (int64_t)B * p.h * p.n;
     dim3 grid((unsigned)ceil_div(p.n, 4 * SM_OW), (unsigned)p.h, (unsigned)B);
     hipStream_t st = (hipStream_t)stream;
-    if (WIDE) {
+    if (SET == SM_NOPOS) {
+        switch (DP) {
+            case 16: softmax_launch<4, PASS>(p, grid, st); break;
+            case 32: softmax_launch<8, PASS>(p, grid, st); break;
+            case 48: softmax_launch<12, PASS>(p, grid, st); break;
+            case 64: softmax_launch<16, PASS>(p, grid, st); break;
+            case 96: softmax_launch<24, PASS>(p, grid, st); break;
+            default: return GT_ENOTSUP;
+        }
+    } else if (SET == SM_WIDE) {
         switch (DP) {
             case 68: softmax_launch<17, PASS>(p, grid, st); break;
             case 100: softmax_launch<25, PASS>(p, grid, st); break;
@@ -457,21 +493,21 @@ extern "C" int gt_softmax_attn_fwd(const float* Q, const float* K, const float* 
                                    int32_t h, int32_t DP, float scale, const float* mask, const gt_dropout* drop,
                                    void* stream) {
     SoftmaxP p{Q, nullptr, K, V, O, nullptr, nullptr, L, 0, nullptr, mask, DropDev{}, n, h, scale};
-    return softmax_attn<SM_FWD, false>(p, B, DP, drop, stream);
+    return softmax_attn<SM_FWD, SM_NARROW>(p, B, DP, drop, stream);
 }
 
 extern "C" int gt_softmax_attn_bwd_q(const float* dO, const float* O, const float* Q, const float* K, const float* V,
                                      const float* L, float* D, float* dQ, int32_t B, int32_t n, int32_t h, int32_t DP,
                                      float scale, const float* mask, const gt_dropout* drop, void* stream) {
     SoftmaxP p{Q, dO, K, V, dQ, nullptr, O, const_cast<float*>(L), 0, D, mask, DropDev{}, n, h, scale};
-    return softmax_attn<SM_BWDQ, false>(p, B, DP, drop, stream);
+    return softmax_attn<SM_BWDQ, SM_NARROW>(p, B, DP, drop, stream);
 }
 
 extern "C" int gt_softmax_attn_bwd_kv(const float* K, const float* V, const float* Q, const float* dO, const float* L,
                                       const float* D, float* dK, float* dV, int32_t B, int32_t n, int32_t h, int32_t DP,
                                       float scale, const float* mask, const gt_dropout* drop, void* stream) {
     SoftmaxP p{K, V, Q, dO, dV, dK, nullptr, const_cast<float*>(L), 0, const_cast<float*>(D), mask, DropDev{}, n, h, scale};
-    return softmax_attn<SM_BWDKV, false>(p, B, DP, drop, stream);
+    return softmax_attn<SM_BWDKV, SM_NARROW>(p, B, DP, drop, stream);
 }
 
 // The same three passes at DP = 68 / 100: entry points of their own, so that the narrow ones keep answering GT_ENOTSUP there.
@@ -479,21 +515,43 @@ extern "C" int gt_softmax_attn_wide_fwd(const float* Q, const float* K, const fl
                                         int32_t h, int32_t DP, float scale, const float* mask, const gt_dropout* drop,
                                         void* stream) {
     SoftmaxP p{Q, nullptr, K, V, O, nullptr, nullptr, L, 0, nullptr, mask, DropDev{}, n, h, scale};
-    return softmax_attn<SM_FWD, true>(p, B, DP, drop, stream);
+    return softmax_attn<SM_FWD, SM_WIDE>(p, B, DP, drop, stream);
 }
 
 extern "C" int gt_softmax_attn_wide_bwd_q(const float* dO, const float* O, const float* Q, const float* K, const float* V,
                                           const float* L, float* D, float* dQ, int32_t B, int32_t n, int32_t h, int32_t DP,
                                           float scale, const float* mask, const gt_dropout* drop, void* stream) {
     SoftmaxP p{Q, dO, K, V, dQ, nullptr, O, const_cast<float*>(L), 0, D, mask, DropDev{}, n, h, scale};
-    return softmax_attn<SM_BWDQ, true>(p, B, DP, drop, stream);
+    return softmax_attn<SM_BWDQ, SM_WIDE>(p, B, DP, drop, stream);
 }
 
 extern "C" int gt_softmax_attn_wide_bwd_kv(const float* K, const float* V, const float* Q, const float* dO, const float* L,
                                            const float* D, float* dK, float* dV, int32_t B, int32_t n, int32_t h, int32_t DP,
                                            float scale, const float* mask, const gt_dropout* drop, void* stream) {
     SoftmaxP p{K, V, Q, dO, dV, dK, nullptr, const_cast<float*>(L), 0, const_cast<float*>(D), mask, DropDev{}, n, h, scale};
-    return softmax_attn<SM_BWDKV, true>(p, B, DP, drop, stream);
+    return softmax_attn<SM_BWDKV, SM_WIDE>(p, B, DP, drop, stream);
+}
+
+// The same three passes on tail-free head tiles, DP = d_k in {16, 32, 48, 64, 96}: no coordinate and no pad columns.
+extern "C" int gt_softmax_attn_nopos_fwd(const float* Q, const float* K, const float* V, float* O, float* L, int32_t B, int32_t n,
+                                         int32_t h, int32_t DP, float scale, const float* mask, const gt_dropout* drop,
+                                         void* stream) {
+    SoftmaxP p{Q, nullptr, K, V, O, nullptr, nullptr, L, 0, nullptr, mask, DropDev{}, n, h, scale};
+    return softmax_attn<SM_FWD, SM_NOPOS>(p, B, DP, drop, stream);
+}
+
+extern "C" int gt_softmax_attn_nopos_bwd_q(const float* dO, const float* O, const float* Q, const float* K, const float* V,
+                                           const float* L, float* D, float* dQ, int32_t B, int32_t n, int32_t h, int32_t DP,
+                                           float scale, const float* mask, const gt_dropout* drop, void* stream) {
+    SoftmaxP p{Q, dO, K, V, dQ, nullptr, O, const_cast<float*>(L), 0, D, mask, DropDev{}, n, h, scale};
+    return softmax_attn<SM_BWDQ, SM_NOPOS>(p, B, DP, drop, stream);
+}
+
+extern "C" int gt_softmax_attn_nopos_bwd_kv(const float* K, const float* V, const float* Q, const float* dO, const float* L,
+                                            const float* D, float* dK, float* dV, int32_t B, int32_t n, int32_t h, int32_t DP,
+                                            float scale, const float* mask, const gt_dropout* drop, void* stream) {
+    SoftmaxP p{K, V, Q, dO, dV, dK, nullptr, const_cast<float*>(L), 0, const_cast<float*>(D), mask, DropDev{}, n, h, scale};
+    return softmax_attn<SM_BWDKV, SM_NOPOS>(p, B, DP, drop, stream);
 }
 
 static int row_softmax_check(const void* a, const void* b, int64_t rows, int32_t n, const gt_dropout* drop) {

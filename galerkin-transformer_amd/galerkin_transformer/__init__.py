@@ -11,7 +11,8 @@ from .model import *           # noqa: F401,F403
 from .model import (GAT, GCN, FourierTransformer, FourierTransformer2D, FourierTransformer2DLite,  # noqa: F401
                     FourierTransformerEncoderLayer, PointwiseRegressor, RandomFeatureEncoderLayer,
                     RandomFeatureTransformer, SimpleTransformer,
-                    SimpleTransformerEncoderLayer, SpectralRegressor)
+                    SimpleTransformerEncoderLayer, SpectralRegressor, TransformerEncoderWrapper,
+                    _TransformerEncoderLayer)
 
 from .ft import (BurgersDataset, DarcyDataset, UnitGaussianNormalizer, WeightedL2Loss,  # noqa: F401
                  WeightedL2Loss2d)

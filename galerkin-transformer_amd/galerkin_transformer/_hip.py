@@ -159,6 +159,12 @@ _PROTOS = {
                                                                            C.POINTER(GtDropout), C.c_void_p]),
     "gt_softmax_attn_wide_bwd_kv": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 4 + [C.c_float, C.c_void_p,
                                                                             C.POINTER(GtDropout), C.c_void_p]),
+    "gt_softmax_attn_nopos_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.POINTER(GtDropout),
+                                                                          C.c_void_p]),
+    "gt_softmax_attn_nopos_bwd_q": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 4 + [C.c_float, C.c_void_p,
+                                                                            C.POINTER(GtDropout), C.c_void_p]),
+    "gt_softmax_attn_nopos_bwd_kv": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 4 + [C.c_float, C.c_void_p,
+                                                                             C.POINTER(GtDropout), C.c_void_p]),
     "gt_row_softmax_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(GtDropout),
                                                          C.c_void_p]),
     "gt_row_softmax_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(GtDropout),
@@ -1740,6 +1746,7 @@ def fourier_attn(F1, F2, T1, T2, B: int, n: int, h: int, DP: int, scale: float, 
 # ----------------------------------------------------------------------------------- softmax attention (gt_softmax.hip)
 SOFTMAX_DP = FOURIER_DP       # head-tile widths of the fused softmax kernels: 16*NF + 4
 SOFTMAX_DP_WIDE = (68, 100)   # d_k = 64 / 96: the same kernels behind entry points of their own (gt_softmax_attn_wide_*)
+SOFTMAX_DP_NOPOS = (16, 32, 48, 64, 96)   # tail-free tiles, DP = d_k, no coordinate columns (gt_softmax_attn_nopos_*)
 
 
 def _softmax_sym(DP: int, tail: str) -> str:
@@ -1748,30 +1755,37 @@ def _softmax_sym(DP: int, tail: str) -> str:
     return ("gt_softmax_attn_wide_" if DP in SOFTMAX_DP_WIDE else "gt_softmax_attn_") + tail
 
 
+def _softmax_entry(DP: int, tail: str) -> str:
+    """The entry point softmax_attn_fwd / softmax_attn_bwd launch: the tail-free one for a tile exactly d_k wide
+    (SOFTMAX_DP_NOPOS), else _softmax_sym's."""
+    return "gt_softmax_attn_nopos_" + tail if DP in SOFTMAX_DP_NOPOS else _softmax_sym(DP, tail)
+
+
 def softmax_attn_fwd(Q, K, V, B: int, n: int, h: int, DP: int, scale: float, mask, drop, O=None, L=None):
-    """gt_softmax_attn_fwd (DP 68 / 100: gt_softmax_attn_wide_fwd) on head tiles [B*n, h, DP]: returns (O, L), L [2, B, h, n]:
+    """gt_softmax_attn_fwd (DP 68 / 100: gt_softmax_attn_wide_fwd; DP 16 ... 96 without tail: gt_softmax_attn_nopos_fwd) on head tiles [B*n, h, DP]: returns (O, L), L [2, B, h, n]:
     L[0] = row maximum + log row sum, L[1] its rounding residual (gt_hip.h)."""
     need_f32_cuda(Q, K, V, mask, O, L)
     if O is None:
         O = torch.empty(B * n, h, DP, dtype=torch.float32, device=Q.device)
     if L is None:
         L = torch.empty(2, B, h, n, dtype=torch.float32, device=Q.device)
-    _launch(_softmax_sym(DP, "fwd"), Q, K, V, O, L, B, n, h, DP, scale, mask, drop,
+    _launch(_softmax_entry(DP, "fwd"), Q, K, V, O, L, B, n, h, DP, scale, mask, drop,
             flops=4.0 * B * h * n * n * DP, nbytes=16.0 * B * n * h * DP, shape=(B, n, h, DP))
     return O, L
 
 
 def softmax_attn_bwd(dO, O, Q, K, V, L, B: int, n: int, h: int, DP: int, scale: float, mask, drop, dQ=None, dK=None,
                      dV=None):
-    """gt_softmax_attn_bwd_q, then gt_softmax_attn_bwd_kv (which reads the D of the first; DP 68 / 100: the _wide_ pair):
+    """gt_softmax_attn_bwd_q, then gt_softmax_attn_bwd_kv (which reads the D of the first; DP 68 / 100: the _wide_ pair; tail-free DP: the _nopos_
+    pair):
     returns (dQ, dK, dV, D)."""
     need_f32_cuda(dO, O, Q, K, V, L, mask, dQ, dK, dV)
     dev = Q.device
     dQ, dK, dV = (torch.empty(B * n, h, DP, dtype=torch.float32, device=dev) if t is None else t for t in (dQ, dK, dV))
     D = torch.empty(B, h, n, dtype=torch.float32, device=dev)
-    _launch(_softmax_sym(DP, "bwd_q"), dO, O, Q, K, V, L, D, dQ, B, n, h, DP, scale, mask, drop,
+    _launch(_softmax_entry(DP, "bwd_q"), dO, O, Q, K, V, L, D, dQ, B, n, h, DP, scale, mask, drop,
             flops=6.0 * B * h * n * n * DP, nbytes=24.0 * B * n * h * DP, shape=(B, n, h, DP))
-    _launch(_softmax_sym(DP, "bwd_kv"), K, V, Q, dO, L, D, dK, dV, B, n, h, DP, scale, mask, drop,
+    _launch(_softmax_entry(DP, "bwd_kv"), K, V, Q, dO, L, D, dK, dV, B, n, h, DP, scale, mask, drop,
             flops=8.0 * B * h * n * n * DP, nbytes=24.0 * B * n * h * DP, shape=(B, n, h, DP))
     return dQ, dK, dV, D
 

@@ -98,6 +98,81 @@ class SimpleTransformerEncoderLayer(nn.Module):
 FourierTransformerEncoderLayer = SimpleTransformerEncoderLayer
 
 
+class _TransformerEncoderLayer(nn.Module):
+    """The classic post-LN Transformer encoder layer around nn.MultiheadAttention, batch first (reference model.py:244-322):
+        src <- [norm1](src + drop1(out_proj(attention(src))));  src <- [norm2](src + drop2(linear2(drop(relu(linear1(src))))))
+    with P = softmax(q k^T / sqrt(d_k)) and the module's own dropout on P in training.  Parameters, state_dict keys and
+    initialisation are the reference's (self_attn.in_proj_weight / in_proj_bias / out_proj.*, linear1, linear2, norm1,
+    norm2; both norms exist even with layer_norm=False).  ``self_attn`` only holds the parameters: its forward is never
+    called, the attention runs on ops.multihead_attention (tail-free fused softmax kernels; the materialised route with
+    attn_weight=True, which returns the head mean of the dropped-out P, detached).
+
+    forward(src, pos=None, weight=None, src_mask=None, src_key_padding_mask=None): ``pos`` is concatenated in FRONT of
+    src and the width must then be d_model (AssertionError otherwise, as torch's); ``weight`` is ignored, as in the
+    reference; the reference uses the masks only when both are given -- that raises NotImplementedError here, one alone is
+    ignored.  set_attention_dropout does not act on this layer."""
+
+    def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0.1, layer_norm=True, attn_weight=False):
+        super().__init__()
+        self.self_attn = nn.MultiheadAttention(d_model, nhead, dropout=dropout)
+        self.linear1 = nn.Linear(d_model, dim_feedforward)
+        self.dropout = nn.Dropout(dropout)
+        self.linear2 = nn.Linear(dim_feedforward, d_model)
+        self.norm1 = nn.LayerNorm(d_model)
+        self.norm2 = nn.LayerNorm(d_model)
+        self.dropout1 = nn.Dropout(dropout)
+        self.dropout2 = nn.Dropout(dropout)
+        self.add_layer_norm = layer_norm
+        self.attn_weight = attn_weight
+        self.activation = nn.ReLU()
+
+    def _pack_groups(self):
+        return []       # in_proj_weight / in_proj_bias are packed parameters already
+
+    def forward(self, src, pos=None, weight=None, src_mask=None, src_key_padding_mask=None):
+        if pos is not None:
+            src = torch.cat([pos, src], dim=-1)
+        mha = self.self_attn
+        assert src.size(-1) == mha.embed_dim, \
+            f"was expecting embedding dimension of {mha.embed_dim}, but got {src.size(-1)}"
+        if src_mask is not None and src_key_padding_mask is not None:
+            raise NotImplementedError("attention masks are outside the HIP hot path")
+        train = self.training
+        src, w = ops.multihead_attention(src, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias,
+                                         n_head=mha.num_heads, p_attn=mha.dropout if train else 0.0, res=src,
+                                         p_out=self.dropout1.p if train else 0.0, need_weights=bool(self.attn_weight))
+        if self.add_layer_norm:
+            src = ops.layer_norm(src, self.norm1.weight, self.norm1.bias, self.norm1.eps)
+        src = ops.feed_forward(src, self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias, res=src,
+                               act="relu", p_h=self.dropout.p if train else 0.0, p_out=self.dropout2.p if train else 0.0)
+        if self.add_layer_norm:
+            src = ops.layer_norm(src, self.norm2.weight, self.norm2.bias, self.norm2.eps)
+        return (src, w) if self.attn_weight else src
+
+
+class TransformerEncoderWrapper(nn.Module):
+    """num_layers deep copies of an encoder layer, then ``norm`` if given (reference model.py:325-373)."""
+
+    __constants__ = ['norm']
+
+    def __init__(self, encoder_layer, num_layers, norm=None):
+        super().__init__()
+        self.layers = nn.ModuleList([copy.deepcopy(encoder_layer) for _ in range(num_layers)])
+        self.num_layers = num_layers
+        self.norm = norm
+
+    def forward(self, src, mask=None, src_key_padding_mask=None):
+        output = src
+        for mod in self.layers:
+            output = mod(output, src_mask=mask, src_key_padding_mask=src_key_padding_mask)
+        if self.norm is not None:
+            if isinstance(self.norm, nn.LayerNorm) and self.norm.elementwise_affine:
+                output = ops.layer_norm(output, self.norm.weight, self.norm.bias, self.norm.eps)
+            else:
+                output = self.norm(output)
+        return output
+
+
 class PointwiseRegressor(nn.Module):
     """[fc(cat[x, grid])] -> num_layers x (Linear + act + dropout) -> Linear   (model.py:472-529)."""
 
@@ -395,7 +470,15 @@ class _ConfiguredModel(nn.Module):
                    out_features=self.n_hidden, activation=self.graph_activation, raw_laplacian=self.raw_laplacian,
                    debug=self.debug)
 
-    def _stack_encoders(self, **extra):
+    def _stack_encoders(self, official=False, **extra):
+        if official and self.attention_type == 'official':
+            # the classic Transformer layer (model.py:888-895); the 1-D model only -- the 2-D models' branch does not run
+            # in the reference
+            layer = _TransformerEncoderLayer(d_model=self.n_hidden, nhead=self.n_head,
+                                             dim_feedforward=self.dim_feedforward, layer_norm=self.layer_norm,
+                                             attn_weight=self.return_attn_weight, dropout=self.encoder_dropout)
+            self.encoder_layers = nn.ModuleList([copy.deepcopy(layer) for _ in range(self.num_encoder_layers)])
+            return
         if self.attention_type not in self._hip_attention:
             raise NotImplementedError(f"attention_type={self.attention_type!r}: only the galerkin / fourier / linear / softmax "
                                       "encoders are on the HIP hot path")
@@ -434,7 +517,7 @@ class SimpleTransformer(_ConfiguredModel):
         self.spacial_fc = default(self.spacial_fc, False)
         self.feat_extract = (self._graph_extractor(self.node_feats)
                              or Identity(in_features=self.node_feats, out_features=self.n_hidden))
-        self._stack_encoders(norm_type=self.norm_type, batch_norm=self.batch_norm,
+        self._stack_encoders(official=True, norm_type=self.norm_type, batch_norm=self.batch_norm,
                              symmetric_init=self.symmetric_init, attn_weight=self.return_attn_weight,
                              residual_type=self.residual_type, activation_type=self.attn_activation)
         if self.n_freq_targets and self.n_freq_targets > 0:

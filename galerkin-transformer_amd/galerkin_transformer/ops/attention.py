@@ -1,5 +1,6 @@
 """The attention node: dropout mode and mask queue, the shared projection stage, the galerkin / linear, fourier and
-softmax cores, SimpleAttentionFn; CrossAttentionFn (query, key, value not one tensor) on the same cores.
+softmax cores, SimpleAttentionFn; multihead_attention (the classic Transformer layer's attention) as a softmax node without
+coordinates; CrossAttentionFn (query, key, value not one tensor) on the same cores.
 """
 from __future__ import annotations
 
@@ -419,10 +420,11 @@ class SimpleAttentionFn(Function):
         dev = x.device
         if kind == "linear" and not H.linattn_supported(dk, p):
             raise H.GtNotSupported(f"linear attention: head size d_k={dk}, pos_dim={p} has no softmax kernel")
-        if kind == "softmax" and DP not in H.SOFTMAX_DP + H.SOFTMAX_DP_WIDE:
+        # (without coordinates the tiles are exactly d_k wide and run on the tail-free instances: ops.multihead_attention)
+        if kind == "softmax" and DP not in H.SOFTMAX_DP + H.SOFTMAX_DP_WIDE and not (p == 0 and DP in H.SOFTMAX_DP_NOPOS):
             raise H.GtNotSupported(f"softmax attention: head tile width round4(d_k + pos_dim) = {DP} has no kernel "
                                    f"(supported: {H.SOFTMAX_DP} and {H.SOFTMAX_DP_WIDE}, i.e. d_k in (16, 32, 48, 64, 96) "
-                                   f"with 1..4 coordinate columns)")
+                                   f"with 1..4 coordinate columns; {H.SOFTMAX_DP_NOPOS} without coordinates)")
         if token_norm:
             if n < 2:       # nn.InstanceNorm1d: "Expected more than 1 spatial element when training"
                 raise ValueError(f"norm_type='instance' needs more than 1 token per sample to normalise over (got n={n})")
@@ -516,6 +518,39 @@ def simple_attention(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, *, kind: str, n_
            bool(need_weights), bool(token_norm))
     out, w = SimpleAttentionFn.apply(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, cfg, mask)
     return out, (w if w.numel() else None)
+
+
+def multihead_attention(x, in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, *, n_head: int,
+                        p_attn: float = 0.0, res=None, sign: float = 1.0, p_out: float = 0.0, need_weights: bool = False,
+                        replay_mask=None):
+    """The attention of the classic Transformer layer (nn.MultiheadAttention with its packed in_proj, batch first):
+        [q, k, v] = x in_proj_weight^T + in_proj_bias, split into n_head heads of d_k = d / n_head
+        P = softmax(q k^T / sqrt(d_k)) over the keys,  Pm = P .* m
+        out = res + sign * dropout_{p_out}( out_proj( merge_heads(Pm v) ) )
+    m: a stateless dropout of rate ``p_attn`` on the softmax OUTPUT, rescaled by 1 / (1 - p_attn) (the caller passes 0 in eval),
+    or the explicit multiplicative ``replay_mask`` [B, h, n, n] (parity tests), or 1.  ``p_attn`` is the caller's own rate: the
+    set_attention_dropout switch, which models the reference's SimpleAttention, is not consulted.
+
+    One SimpleAttentionFn node of kind 'softmax': the shared projection with no coordinates and no head norm (head tiles
+    exactly d_k wide), then the softmax core with out_proj in fc's place.  ``need_weights=False``: the fused tail-free
+    kernels (gt_softmax_attn_nopos_*), no n x n matrix in HBM, returns (out, None).  ``need_weights=True``: the materialised
+    route, returns (out, w) with w [B, n, n] the mean of Pm over the heads (average_attn_weights=True), detached.
+    d_k outside H.SOFTMAX_DP_NOPOS raises GtNotSupported before anything is launched."""
+    h = int(n_head)
+    assert x.dim() == 3 and x.size(-1) % h == 0, "multihead_attention: x is [B, n, d] with d divisible by n_head"
+    dk = x.size(-1) // h
+    if dk not in H.SOFTMAX_DP_NOPOS:
+        raise H.GtNotSupported(f"multihead_attention: head width d_k = {dk} has no kernel (supported: {H.SOFTMAX_DP_NOPOS})")
+    _check_res_is_x(res, x, "multihead_attention")
+    mask = None
+    if replay_mask is not None:
+        mask = _c(replay_mask.to(device=x.device, dtype=torch.float32))
+        assert mask.shape == (x.size(0), h, x.size(1), x.size(1)), "multihead_attention: replay_mask is [B, h, n, n]"
+    cfg = ("softmax", h, 0, 0.0, float(sign), 0.0 if mask is not None else float(p_attn), float(p_out), bool(need_weights),
+           False)
+    out, w = SimpleAttentionFn.apply(x, None, in_proj_weight, in_proj_bias, None, None, out_proj_weight, out_proj_bias, res,
+                                     cfg, mask)
+    return out, (w.mean(dim=1) if w.numel() else None)
 
 
 # ----------------------------------------------------------------------------------- cross-attention

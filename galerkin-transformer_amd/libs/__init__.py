@@ -4,3 +4,4 @@ from galerkin_transformer.utils import *       # noqa: F401,F403
 from galerkin_transformer.utils_ft import *    # noqa: F401,F403
 from galerkin_transformer.ft import *          # noqa: F401,F403
 from galerkin_transformer.model import *       # noqa: F401,F403
+from galerkin_transformer.model import _TransformerEncoderLayer      # noqa: F401  (underscored: not in the star import)

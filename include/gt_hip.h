@@ -554,6 +554,10 @@ int gt_dropout_block16(float* S, int64_t BH, int32_t n, const gt_dropout* drop, 
  *     gt_softmax_attn_wide_fwd / _wide_bwd_q / _wide_bwd_kv: the same three passes, arguments and contracts for the 64- and
  *     96-wide heads, DP in {68, 100}, else GT_ENOTSUP (the narrow entry points keep returning GT_ENOTSUP at these widths).
  *     One block per CU (68 / 100 KiB of LDS stream tiles per block).
+ *     gt_softmax_attn_nopos_fwd / _nopos_bwd_q / _nopos_bwd_kv: the same three passes, arguments and contracts on TAIL-FREE head
+ *     tiles, exactly DP = d_k floats wide with no coordinate and no pad columns (the classic Transformer layer,
+ *     ops.multihead_attention): DP in {16, 32, 48, 64, 96}, else GT_ENOTSUP.  Every column of the tile is a value column and
+ *     takes part in both products; L and its residual are written as by gt_softmax_attn_fwd.
  *
  * Materialised route (the caller wants Pm back): S by gt_gemm, then one wave per row of the [rows][n] matrix:
  *     gt_row_softmax_fwd       P = softmax(S) (maximum subtracted), Pm = P .* m;  P == S and (no mask, no dropout) Pm == P allowed
@@ -577,6 +581,14 @@ int gt_softmax_attn_wide_bwd_q(const float* dO, const float* O, const float* Q, 
 int gt_softmax_attn_wide_bwd_kv(const float* K, const float* V, const float* Q, const float* dO, const float* L,
                                 const float* D, float* dK, float* dV, int32_t B, int32_t n, int32_t h, int32_t DP, float scale,
                                 const float* mask, const gt_dropout* drop, void* stream);
+int gt_softmax_attn_nopos_fwd(const float* Q, const float* K, const float* V, float* O, float* L, int32_t B, int32_t n,
+                              int32_t h, int32_t DP, float scale, const float* mask, const gt_dropout* drop, void* stream);
+int gt_softmax_attn_nopos_bwd_q(const float* dO, const float* O, const float* Q, const float* K, const float* V, const float* L,
+                                float* D, float* dQ, int32_t B, int32_t n, int32_t h, int32_t DP, float scale,
+                                const float* mask, const gt_dropout* drop, void* stream);
+int gt_softmax_attn_nopos_bwd_kv(const float* K, const float* V, const float* Q, const float* dO, const float* L,
+                                 const float* D, float* dK, float* dV, int32_t B, int32_t n, int32_t h, int32_t DP, float scale,
+                                 const float* mask, const gt_dropout* drop, void* stream);
 int gt_row_softmax_fwd(const float* S, float* P, float* Pm, int64_t rows, int32_t n, int64_t row0, const float* mask,
                        const gt_dropout* drop, void* stream);
 int gt_row_softmax_bwd(const float* P, const float* dPm, float* dS, int64_t rows, int32_t n, int64_t row0, const float* mask,

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INC = os.path.join(os.path.dirname(HERE), "include")
 OUT_DIR = os.path.join(HERE, "galerkin_transformer", "_lib")
-SOURCES = ["gt_gemm.hip", "gt_gemm_desc.hip", "gt_gemm_x3.hip", "gt_gemm_x3p.hip", "gt_gemm_x3w.hip", "gt_ops.hip", "gt_headnorm.hip", "gt_galerkin.hip", "gt_layernorm.hip", "gt_modemix.hip", "gt_resize.hip", "gt_convresize.hip", "gt_fourier.hip", "gt_fourier16.hip", "gt_dft.hip", "gt_tsmm.hip", "gt_head.hip", "gt_optim.hip", "gt_convw.hip", "gt_ffn.hip", "gt_linattn.hip", "gt_tokennorm.hip", "gt_batchnorm.hip", "gt_softmax.hip", "gt_loss.hip", "gt_pool.hip", "gt_deconv.hip", "gt_graphconv.hip", "gt_graphattn.hip", "gt_rfattn.hip"]
+SOURCES = ["gt_gemm.hip", "gt_gemm_desc.hip", "gt_gemm_x3.hip", "gt_gemm_x3p.hip", "gt_gemm_x3w.hip", "gt_ops.hip", "gt_headnorm.hip", "gt_galerkin.hip", "gt_layernorm.hip", "gt_modemix.hip", "gt_resize.hip", "gt_convresize.hip", "gt_fourier.hip", "gt_fourier16.hip", "gt_dft.hip", "gt_tsmm.hip", "gt_head.hip", "gt_optim.hip", "gt_convw.hip", "gt_ffn.hip", "gt_linattn.hip", "gt_tokennorm.hip", "gt_batchnorm.hip", "gt_softmax.hip", "gt_loss.hip", "gt_pool.hip", "gt_deconv.hip", "gt_graphconv.hip", "gt_graphattn.hip", "gt_rfattn.hip", "gt_causal.hip"]
 HEADERS = [os.path.join(CSRC, "gt_common.h"), os.path.join(CSRC, "gt_gemm_core.h"), os.path.join(CSRC, "gt_x3_core.h"), os.path.join(CSRC, "gt_resize_core.h"), os.path.join(CSRC, "gt_colpass.h"), os.path.join(INC, "gt_hip.h")]
 ARCH = "gfx950"
 

@@ -9,7 +9,7 @@ from .layers import (EdgeEncoder, FeedForward, GraphAttention, GraphConvolution,
                      get_attention_dropout, push_attention_masks, set_attention_dropout)
 from .model import *           # noqa: F401,F403
 from .model import (GAT, GCN, FourierTransformer, FourierTransformer2D, FourierTransformer2DLite,  # noqa: F401
-                    FourierTransformerEncoderLayer, PointwiseRegressor, RandomFeatureEncoderLayer,
+                    FourierTransformerEncoderLayer, GalerkinTransformerDecoderLayer, PointwiseRegressor, RandomFeatureEncoderLayer,
                     RandomFeatureTransformer, SimpleTransformer,
                     SimpleTransformerEncoderLayer, SpectralRegressor, TransformerEncoderWrapper,
                     _TransformerEncoderLayer)

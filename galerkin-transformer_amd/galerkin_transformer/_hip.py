@@ -278,6 +278,10 @@ _PROTOS = {
                              [C.c_int32] * 3 + [C.c_float, C.POINTER(GtDropout), C.c_void_p]),
     "gt_graphattn_weights": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
                                                          C.POINTER(GtDropout), C.c_void_p]),
+    "gt_causal_attn_state_bytes": (C.c_int64, [C.c_int32] * 4),
+    "gt_causal_attn_bwd_ws_bytes": (C.c_int64, [C.c_int32] * 4),
+    "gt_causal_attn_fwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
+    "gt_causal_attn_bwd": (C.c_int, [C.c_void_p] * 11 + [C.c_int32] * 5 + [C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
@@ -1810,6 +1814,54 @@ def row_softmax_bwd(P, dPm, rows: int, n: int, mask, drop, dS=None, row0: int = 
         dS = torch.empty_like(P)
     _launch("gt_row_softmax_bwd", P, dPm, dS, rows, n, row0, mask, drop, nbytes=12.0 * P.numel())
     return dS
+
+
+# ----------------------------------------------------------------------------------- causal linear attention (gt_causal.hip)
+CAUSAL_DP = (16, 32, 48, 64, 96, 20, 36, 52, 68, 100)      # head-tile widths: d_k alone, and d_k with 1..4 coordinate columns
+
+
+def causal_check(DP: int):
+    """The width refusal of the causal kernels, raised before anything is allocated or launched (no device needed)."""
+    if DP not in CAUSAL_DP:
+        raise GtNotSupported(f"causal linear attention: no kernel for head tile width {DP} (supported: {CAUSAL_DP}, i.e. "
+                             "d_k in (16, 32, 48, 64, 96) alone or with 1..4 coordinate columns)")
+
+
+def _causal_keep(keep, B: int, n: int):
+    if keep is not None and not (keep.is_cuda and keep.dtype == torch.uint8 and keep.is_contiguous()
+                                 and keep.shape == (B, n)):
+        raise TypeError("causal attention: the keep vector is a contiguous uint8 device tensor [B, n]")
+    return keep
+
+
+def causal_attn_fwd(Q, K, V, keep, B: int, n: int, h: int, DP: int, eps: float, O=None):
+    """gt_causal_attn_fwd on head tiles [B*n, h, DP] and keep [B, n] (uint8) or None: returns (O, den [B, h, n], states), the
+    exclusive per-chunk prefix states that causal_attn_bwd reads."""
+    causal_check(DP)
+    need_f32_cuda(Q, K, V, O)
+    keep = _causal_keep(keep, B, n)
+    dev = Q.device
+    if O is None:
+        O = torch.empty(B * n, h, DP, dtype=torch.float32, device=dev)
+    den = torch.empty(B, h, n, dtype=torch.float32, device=dev)
+    states = torch.empty(lib().gt_causal_attn_state_bytes(B, n, h, DP) // 4, dtype=torch.float32, device=dev)
+    _launch("gt_causal_attn_fwd", Q, K, V, keep, O, den, B, n, h, DP, float(eps), states, states.numel() * 4,
+            flops=2.0 * B * h * n * DP * (2 * DP + 2 * 64), nbytes=16.0 * B * n * h * DP, shape=(B, n, h, DP))
+    return O, den, states
+
+
+def causal_attn_bwd(dO, O, Q, K, V, keep, den, states, B: int, n: int, h: int, DP: int, D: int, eps: float, dQ=None,
+                    dK=None, dV=None):
+    """gt_causal_attn_bwd: returns (dQ, dK, dV) [B*n, h, DP] with exact zeros in the columns D .. DP-1."""
+    causal_check(DP)
+    need_f32_cuda(dO, O, Q, K, V, den, states, dQ, dK, dV)
+    keep = _causal_keep(keep, B, n)
+    dev = Q.device
+    dQ, dK, dV = (torch.empty(B * n, h, DP, dtype=torch.float32, device=dev) if t is None else t for t in (dQ, dK, dV))
+    ws = workspace(dev, max(16, lib().gt_causal_attn_bwd_ws_bytes(B, n, h, DP)))
+    _launch("gt_causal_attn_bwd", dO, O, Q, K, V, keep, den, states, dQ, dK, dV, B, n, h, DP, D, float(eps), ws=ws,
+            flops=2.0 * B * h * n * DP * (5 * DP + 5 * 64), nbytes=36.0 * B * n * h * DP, shape=(B, n, h, DP))
+    return dQ, dK, dV
 
 
 # ----------------------------------------------------------------------------------- 2-D training objective

@@ -32,6 +32,7 @@ def default(value, d):
 _LINEAR_FAMILY = ("linear", "galerkin", "global")
 _HIP_ATTENTION = ("galerkin", "fourier", "integral", "local", "linear", "global")
 _SOFTMAX_ATTENTION = ("softmax",)      # on the HIP path too, with coordinates only (SimpleAttention.fused_forward)
+_CAUSAL_ATTENTION = ("causal",)        # causal linear attention (the decoder layer's second block), with or without coordinates
 
 
 def _act_module(name, fallback="silu"):
@@ -526,6 +527,16 @@ class SimpleAttention(nn.Module):
     counts are equal) and divides K'^T V' -- a sum over the n_kv memory tokens -- by n_q, as the reference does
     (layers.py:719, 728); fourier / softmax need n_q == n_kv (NotImplementedError otherwise).  Unequal key / value token
     counts, unequal batch sizes and ``pos`` with n_q != n_kv are AssertionErrors.
+    'causal' (causal linear attention, reference layers.py:736-762; fp32 arithmetic in every precision mode, linear in n):
+    with k^_j = keep_j K'_j / n and v^_j = keep_j V'_j, head output i is (sum_{j<=i} k^_j v^_j^T)^T Q'_i divided by
+    (sum_{j<=i} k^_j + 1e-7) . Q'_i; ``norm_Q`` / ``norm_K`` as for fourier.  Head tiles round4(d_k + pos_dim) in {16, 32, 48,
+    64, 96} (no coordinates) or {20, 36, 52, 68, 100}; self-attention and (query, key, value) with n_q == n_kv
+    (AssertionError otherwise).  Three deviations from the reference, whose call sites of this kind do not run
+    (INTEGRATION.md): ``mask`` is handed to the core as its ``kv_mask`` -- a torch.bool tensor [B, n_kv], True = keep, None
+    keeps every token, not unsqueezed; anything else is a TypeError / AssertionError before a launch.  The reference's
+    F.dropout(p = 0.5) acts on the [B, h, n, D, D] running state, which never exists here: no attention dropout is drawn,
+    set_attention_dropout is not consulted, and ``attn_weight`` is None.  The operator is only as well-conditioned as its
+    denominators (a sum of signed terms).
     Other variants of the reference are baselines outside the hot path."""
 
     def __init__(self, n_head, d_model, pos_dim: int = 1, attention_type="fourier", dropout=0.1,
@@ -620,9 +631,9 @@ class SimpleAttention(nn.Module):
         if self.attention_type in _SOFTMAX_ATTENTION and (pos is None or self.pos_dim == 0):
             raise NotImplementedError("attention_type='softmax' without coordinates is outside the HIP hot path: the softmax "
                                       "kernels take head tiles of width 16*k + 4 (d_k in (16, 32, 48, 64, 96) plus pos_dim >= 1)")
-        if self.attention_type not in _HIP_ATTENTION + _SOFTMAX_ATTENTION:
+        if self.attention_type not in _HIP_ATTENTION + _SOFTMAX_ATTENTION + _CAUSAL_ATTENTION:
             raise NotImplementedError(f"attention_type={self.attention_type!r} is outside the HIP hot path "
-                                      "(galerkin / fourier / linear / softmax only)")
+                                      "(galerkin / fourier / linear / softmax / causal only)")
         use_pos = pos is not None and self.pos_dim > 0
         if use_pos:
             assert pos.size(-1) == self.pos_dim
@@ -642,37 +653,60 @@ class SimpleAttention(nn.Module):
             kind = "linear"
         elif self.attention_type in _SOFTMAX_ATTENTION:
             kind = "softmax"
+        elif self.attention_type in _CAUSAL_ATTENTION:
+            kind = "causal"
+            # the width refusal needs no device: NotImplementedError("... no kernel ...") before anything else happens
+            H.causal_check(H.round4(self.d_k + (self.pos_dim if use_pos else 0)))
         else:
             kind = "fourier"
         return pos, wfc, bfc, kind
 
-    def fused_forward(self, x, pos=None, residual=None, sign=1.0, p_out=0.0, need_weights=True):
+    def fused_forward(self, x, pos=None, residual=None, sign=1.0, p_out=0.0, need_weights=True, kv_mask=None):
         """res + sign*dropout(attention(x)); the encoder layer's entry point.  ``need_weights=False`` lets the
-        Fourier and softmax types run fused (no n x n matrix in HBM; the returned weight is None)."""
+        Fourier and softmax types run fused (no n x n matrix in HBM; the returned weight is None).  ``kv_mask``: the
+        causal type's key / value mask (torch.bool [B, n], True = keep)."""
         pos, wfc, bfc, kind = self._operator_args(pos, x.device)
+        keep = self._keep_vector(kv_mask, x)
         wqkv, bqkv, gamma, beta, mask = self._packed()
         out, w = ops.simple_attention(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc,
                                       kind=kind, n_head=self.n_head, norm_mask=mask, eps=self.eps,
                                       res=residual, sign=sign, p_out=p_out, need_weights=need_weights,
-                                      token_norm=self.add_norm and self.norm_type == "instance")
+                                      token_norm=self.add_norm and self.norm_type == "instance", keep=keep)
         self.attn_weight = w
         return out, w
 
-    def fused_forward_cross(self, query, key, value, pos=None, residual=None, sign=1.0, p_out=0.0, need_weights=True):
+    def fused_forward_cross(self, query, key, value, pos=None, residual=None, sign=1.0, p_out=0.0, need_weights=True,
+                            kv_mask=None):
         """The same for query [B, n_q, d], key and value [B, n_kv, d] that are not one tensor (ops.cross_attention):
         res + sign*dropout(attention(query, key, value)) with ``residual`` = ``query`` or None.  Shape contracts are
         AssertionErrors, raised before anything is launched."""
         ops.check_cross_shapes(query, key, value, pos if self.pos_dim > 0 else None)
         pos, wfc, bfc, kind = self._operator_args(pos, query.device)
+        keep = self._keep_vector(kv_mask, key)
         wqkv, bqkv, gamma, beta, mask = self._packed()
         out, w = ops.cross_attention(query, key, value, pos, wqkv, bqkv, gamma, beta, wfc, bfc,
                                      kind=kind, n_head=self.n_head, norm_mask=mask, eps=self.eps,
                                      res=residual, sign=sign, p_out=p_out, need_weights=need_weights,
-                                     token_norm=self.add_norm and self.norm_type == "instance")
+                                     token_norm=self.add_norm and self.norm_type == "instance", keep=keep)
         self.attn_weight = w
         return out, w
 
+    def _keep_vector(self, kv_mask, key):
+        """The causal type's ``mask`` -> the kernels' keep vector [B, n_kv] (uint8) or None; the checks of ops.check_kv_mask."""
+        if kv_mask is None:
+            return None
+        if self.attention_type not in _CAUSAL_ATTENTION:
+            raise ValueError("kv_mask is the key / value mask of attention_type='causal'")
+        return ops.check_kv_mask(kv_mask, key.size(0), key.size(1))
+
     def forward(self, query, key, value, pos=None, mask=None, weight=None):
+        if self.attention_type in _CAUSAL_ATTENTION:
+            # (the reference's call passes mask= to a function that takes kv_mask=, and asserts a mask is given: INTEGRATION.md)
+            if weight is not None:
+                raise NotImplementedError("weighted attention is outside the HIP hot path")
+            if not (query is key and key is value):
+                return self.fused_forward_cross(query, key, value, pos, kv_mask=mask)
+            return self.fused_forward(query, pos, kv_mask=mask)
         if mask is not None:
             if self.attention_type in _LINEAR_FAMILY:
                 raise RuntimeError("linear attention does not support casual mask.")

@@ -150,6 +150,72 @@ class _TransformerEncoderLayer(nn.Module):
         return (src, w) if self.attn_weight else src
 
 
+class GalerkinTransformerDecoderLayer(nn.Module):
+    """The decoder layer on causal linear attention (reference model.py:142-241), three post-LN blocks:
+        x <- [norm1](x + drop1(self_attn(x, x, x, mask=tgt_mask)))
+        x <- [norm2](x + drop2(multihead_attn(x, memory, memory, mask=memory_mask)))      attention_type='causal'
+        x <- [norm3](x + drop(ff(x)))
+    Constructor arguments, parameter names and shapes are the reference's: ``self_attn`` / ``multihead_attn`` (each with its
+    ``fc``, which the coordinate-free calls never use), ``ff``, the unused ``linear2``, ``norm1..3`` only with ``layer_norm``.
+    No ``pos`` is passed to either attention.  ``memory`` has as many tokens as ``x`` (AssertionError otherwise).
+
+    The reference's forward does not run (its two attention calls raise TypeError, and the causal branch asserts a mask the
+    decoder does not give); the repairs are SimpleAttention's (its docstring): ``memory_mask`` is the causal
+    core's key / value mask, torch.bool [B, n] with True = keep, or None; ``tgt_mask`` goes to ``self_attn`` as ``mask`` --
+    with the default 'galerkin' a mask that is not None raises the linear family's RuntimeError, with fourier / softmax
+    NotImplementedError, with 'causal' it is that core's key / value mask; the causal core draws no attention dropout."""
+
+    def __init__(self, d_model, nhead, pos_dim=1, dim_feedforward=512, attention_type='galerkin', layer_norm=True,
+                 attn_norm=None, norm_type='layer', norm_eps=1e-5, xavier_init: float = 1e-2,
+                 diagonal_weight: float = 1e-2, dropout=0.05, ffn_dropout=None, activation_type='relu', device=None,
+                 dtype=None, debug=False):
+        super().__init__()
+        factory_kwargs = {'device': device, 'dtype': dtype}
+        ffn_dropout = default(ffn_dropout, dropout)
+        self.debug = debug
+        attn = dict(pos_dim=pos_dim, norm=attn_norm, eps=norm_eps, norm_type=norm_type, diagonal_weight=diagonal_weight,
+                    xavier_init=xavier_init, dropout=dropout)
+        self.self_attn = SimpleAttention(nhead, d_model, attention_type=attention_type, **attn)
+        self.multihead_attn = SimpleAttention(nhead, d_model, attention_type='causal', **attn)
+        dim_feedforward = default(dim_feedforward, 2 * d_model)
+        self.ff = FeedForward(in_dim=d_model, dim_feedforward=dim_feedforward, activation=activation_type,
+                              dropout=ffn_dropout)
+        self.dropout = nn.Dropout(ffn_dropout)
+        self.linear2 = nn.Linear(dim_feedforward, d_model, **factory_kwargs)
+        self.add_layer_norm = layer_norm
+        self.norm_eps = norm_eps
+        if self.add_layer_norm:
+            self.norm1 = nn.LayerNorm(d_model, eps=norm_eps, **factory_kwargs)
+            self.norm2 = nn.LayerNorm(d_model, eps=norm_eps, **factory_kwargs)
+            self.norm3 = nn.LayerNorm(d_model, eps=norm_eps, **factory_kwargs)
+        self.dropout1 = nn.Dropout(dropout)
+        self.dropout2 = nn.Dropout(dropout)
+        self.activation = F.relu
+
+    def _norm(self, norm, x):
+        return ops.layer_norm(x, norm.weight, norm.bias, self.norm_eps)
+
+    def forward(self, x, memory, tgt_mask=None, memory_mask=None):
+        train = self.training
+        sa = self.self_attn
+        if sa.attention_type == 'causal':
+            x = sa.fused_forward(x, None, residual=x, p_out=self.dropout1.p if train else 0.0, kv_mask=tgt_mask)[0]
+        else:
+            if tgt_mask is not None:
+                sa(x, x, x, mask=tgt_mask)      # the refusal of that attention type
+            x = sa.fused_forward(x, None, residual=x, p_out=self.dropout1.p if train else 0.0, need_weights=False)[0]
+        if self.add_layer_norm:
+            x = self._norm(self.norm1, x)
+        x = self.multihead_attn.fused_forward_cross(x, memory, memory, None, residual=x,
+                                                    p_out=self.dropout2.p if train else 0.0, kv_mask=memory_mask)[0]
+        if self.add_layer_norm:
+            x = self._norm(self.norm2, x)
+        x = self.ff.fused_forward(x, residual=x, p_out=self.dropout.p if train else 0.0)
+        if self.add_layer_norm:
+            x = self._norm(self.norm3, x)
+        return x
+
+
 class TransformerEncoderWrapper(nn.Module):
     """num_layers deep copies of an encoder layer, then ``norm`` if given (reference model.py:325-373)."""
 

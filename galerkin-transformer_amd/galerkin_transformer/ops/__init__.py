@@ -21,13 +21,15 @@ One module per operator family; this file only re-exports (every name is the obj
 ``loss``         the weighted-L2 / H1 objectives per sample: ``H1Loss2dFn`` (2-D), ``H1Loss1dFn`` (1-D)
 ``rfattn``       random-feature attention ('rfa' / 'favor'): ``RandomFeatureAttentionFn``, ``random_feature_attention``
 ``attention``    the attention-dropout mode and mask queue, ``SimpleAttentionFn`` with its projection stage and cores,
-                 ``CrossAttentionFn`` on the same cores, ``multihead_attention`` (nn.MultiheadAttention's arithmetic)
+                 ``CrossAttentionFn`` on the same cores, ``multihead_attention`` (nn.MultiheadAttention's arithmetic),
+                 ``causal_linear_attention`` (the causal core alone on [B, h, n, D] tensors)
 """
 from ._handoff import (_fold_masks, _fold_seq, _gate_depth, _gate_fold, _hint_output_mask, _mask_hints,  # noqa: F401
                        _masked_twins, _offer_gate, _offer_twin, _relu_mask_sink, _scaler_mask_sink, _silu_gates,
                        _take_gate, _take_twin, _wanted_mask, set_relu_mask_sink, set_scaler_mask_sink, silu_gate_scope)
-from .attention import (CrossAttentionFn, SimpleAttentionFn, _dkv_ln_fused, _plain_tiles, _qkvnorm_fused,  # noqa: F401
-                        check_cross_shapes, cross_attention, get_attention_dropout, multihead_attention,
+from .attention import (CausalLinearAttnFn, CrossAttentionFn, SimpleAttentionFn, _dkv_ln_fused, _plain_tiles,  # noqa: F401
+                        _qkvnorm_fused, causal_linear_attention, check_cross_shapes, check_kv_mask, cross_attention,
+                        get_attention_dropout, multihead_attention,
                         push_attention_masks, set_attention_dropout, simple_attention)
 from .conv import (Conv3x3NhwcFn, Conv3x3ResizeFn, ScalerConvChainFn, _conv_implicit, _conv_k_order,  # noqa: F401
                    _conv_wgrad, _conv_wgrad_planes, _crb_bits, _gather_cache, _gathered,

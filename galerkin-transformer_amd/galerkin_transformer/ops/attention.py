@@ -1,6 +1,7 @@
-"""The attention node: dropout mode and mask queue, the shared projection stage, the galerkin / linear, fourier and
-softmax cores, SimpleAttentionFn; multihead_attention (the classic Transformer layer's attention) as a softmax node without
-coordinates; CrossAttentionFn (query, key, value not one tensor) on the same cores.
+"""The attention node: dropout mode and mask queue, the shared projection stage, the galerkin / linear, fourier,
+softmax and causal cores, SimpleAttentionFn; multihead_attention (the classic Transformer layer's attention) as a softmax
+node without coordinates; CrossAttentionFn (query, key, value not one tensor) on the same cores; causal_linear_attention,
+the causal core alone on [B, h, n, D] tensors.
 """
 from __future__ import annotations
 
@@ -384,6 +385,33 @@ def _softmax_bwd(s, g, d_attn, dims, sign, hbf, flash):
     return dO3, dwfc, dbfc
 
 
+_CAUSAL_EPS = 1e-7      # causal_linear_attn's default eps (layers.py:736); SimpleAttention does not pass another
+
+
+def _causal_fwd(Qp, Kp, Vp, keep, out, rc, wf, bfc, d_out, dims, sign):
+    """causal core: att_i = S_i^T q_i / den_i with S_i = sum_{j<=i} k^_j v^_j^T, k^ = keep K' / n, v^ = keep V'
+    (gt_causal_attn_fwd: chunked scan, linear in n), out = res + sign * dropout(fc(att)).  ``keep`` [B, n] uint8 or None.  No
+    attention dropout and no attention weight.  Returns (attn_weight = empty, tensors to save): den and the per-chunk prefix
+    states are kept for the backward."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    T, hD = B * n, h * DP
+    att, den, states = H.causal_attn_fwd(Qp, Kp, Vp, keep, B, n, h, DP, _CAUSAL_EPS)
+    att = att.reshape(T, hD)
+    wpad = _merged_fc_fwd(att, out, rc, wf, bfc, d_out, dims, sign)
+    return torch.empty(0, device=out.device), dict(wpad=wpad, att=att, den=den, states=states)
+
+
+def _causal_bwd(s, g, dims, sign, hbf):
+    """Backward of _causal_fwd.  Returns (dO3, dwfc, dbfc)."""
+    B, n, d, h, dk, p, Dr, DP = dims
+    T, dev = B * n, g.device
+    dO3 = torch.empty(3, T, h, DP, dtype=torch.float32, device=dev)
+    datt, dwfc, dbfc = _merged_fc_bwd(s, g, dims, sign, hbf)
+    H.causal_attn_bwd(datt.reshape(T, h, DP), s.att.reshape(T, h, DP), s.out3[0], s.out3[1], s.out3[2], s.keep, s.den,
+                      s.states, B, n, h, DP, Dr, _CAUSAL_EPS, dQ=dO3[0], dK=dO3[1], dV=dO3[2])
+    return dO3, dwfc, dbfc
+
+
 class SimpleAttentionFn(Function):
     """out = res + sign * dropout1( fc( merge_heads( attention(Q', K', V') ) ) ).
 
@@ -391,6 +419,8 @@ class SimpleAttentionFn(Function):
     linear  : the same on Q~ = softmax(Q', dim=-1), K~ = softmax(K', dim=-2)  (layers.py:719-722; 'global' too)
     fourier : per-head LN on Q,K; S = mask .* (Q' K'^T)/sqrt(d_k')/n; heads: S V' (layers.py:672-705)
     softmax : per-head LN on Q,K; P = softmax(Q' K'^T/sqrt(d_k')); heads: (mask .* P) V'  (layers.py:691-703)
+    causal  : per-head LN on Q,K; heads: tril(Q' K^'^T) V^' / (its row sums + eps sum_d q) (layers.py:736-762); the ``mask``
+              argument is then the keep vector [B, n] (uint8) or None, and no attention dropout is drawn
     with X' = [pos, X] per head (layers.py:869-874) and fc over the merged heads (layers.py:894-897).
     token_norm (norm_type='instance', galerkin / linear): K, V are normalised over the TOKENS per (sample, head, channel)
     instead (layers.py:842-854): the projection writes raw tiles, gt_token_norm_fwd normalises their value columns.
@@ -407,15 +437,19 @@ class SimpleAttentionFn(Function):
     @staticmethod
     def forward(ctx, x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, cfg, mask):
         (kind, h, norm_mask, eps, sign, p_attn, p_out, need_w, token_norm) = cfg
-        if kind not in ("galerkin", "linear", "fourier", "softmax"):
+        if kind not in ("galerkin", "linear", "fourier", "softmax", "causal"):
             raise ValueError(f"simple_attention: kind={kind!r}")
-        if token_norm and (kind in ("fourier", "softmax") or norm_mask != 0b110 or gamma is None or beta is None):
+        if token_norm and (kind in ("fourier", "softmax", "causal") or norm_mask != 0b110 or gamma is None or beta is None):
             raise ValueError("simple_attention: token_norm is the K, V norm of the galerkin / linear kinds")
-        H.need_f32_cuda(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, mask)
         B, n, d = x.shape
         dk = d // h
         p = 0 if pos is None else pos.shape[-1]
         Dr, DP = dk + p, H.round4(dk + p)
+        keep = None
+        if kind == "causal":
+            H.causal_check(DP)
+            keep, mask = mask, None     # the keep vector [B, n] (uint8) travels in the mask slot
+        H.need_f32_cuda(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, mask)
         T = B * n
         dev = x.device
         if kind == "linear" and not H.linattn_supported(dk, p):
@@ -451,11 +485,13 @@ class SimpleAttentionFn(Function):
                                          d_attn, d_out, dims, sign)
         elif kind == "softmax":
             attn_w, core, ctx.flash = _softmax_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn, d_out, dims, sign, need_w)
+        elif kind == "causal":
+            attn_w, core = _causal_fwd(Qp, Kp, Vp, keep, out, rc, wf, bfc, d_out, dims, sign)
         else:
             attn_w, core, (ctx.flash, ctx.f16, ctx.block16) = _fourier_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn,
                                                                            d_out, dims, sign, need_w)
         _save_named(ctx, xc=xc, wq=wq, gamma=gamma, beta=beta, qkv=qkv, stats=stats, out3=out3, kvn=kvn, st_k=st_k,
-                    st_v=st_v, mask=mask, **core)
+                    st_v=st_v, mask=mask, keep=keep, **core)
         ctx.plain, ctx.fused_ln = plain, fused_ln
         ctx.cfg, ctx.dims, ctx.salt, ctx.xshape = cfg, dims, salt, x.shape
         ctx.has = (bqkv is not None, bfc is not None, res is not None)
@@ -484,6 +520,8 @@ class SimpleAttentionFn(Function):
                                                 ctx.fused_ln)
         elif kind == "softmax":
             dO3, dwfc, dbfc = _softmax_bwd(s, g, d_attn, ctx.dims, sign, hbf, ctx.flash)
+        elif kind == "causal":
+            dO3, dwfc, dbfc = _causal_bwd(s, g, ctx.dims, sign, hbf)
         else:
             dO3, dwfc, dbfc = _fourier_bwd(s, g, d_attn, ctx.dims, sign, hbf, ctx.flash, ctx.f16, ctx.block16)
         dx, dwqkv, dbqkv, dgamma, dbeta = _project_heads_bwd(s, dO3, ln, g_in, ctx.in_mask, ctx.dims, norm_mask, token_norm,
@@ -493,15 +531,21 @@ class SimpleAttentionFn(Function):
 
 def simple_attention(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc, *, kind: str, n_head: int, norm_mask: int,
                      eps: float, res=None, sign: float = 1.0, p_out: float = 0.0, need_weights: bool = True,
-                     token_norm: bool = False):
+                     token_norm: bool = False, keep=None):
     """Self-attention block; ``res`` must be ``x`` (or None).  Returns (out, attn_weight).  For the Fourier and softmax
     types ``need_weights=False`` selects the fused kernel that never materialises the n x n matrix
     (attn_weight is then None); the Galerkin matrix is small and always returned.  ``token_norm`` (galerkin / linear with
-    norm_mask = K, V): gamma / beta are the affine of the token-axis norm (norm_type='instance') instead of the LayerNorm's."""
+    norm_mask = K, V): gamma / beta are the affine of the token-axis norm (norm_type='instance') instead of the LayerNorm's.
+    kind='causal': ``keep`` [B, n] (uint8, 0 = the key / value token is dropped) or None; the attention dropout mode is not
+    consulted (the reference's dropout acts on the running state, which never exists here) and attn_weight is None."""
     _check_res_is_x(res, x, "simple_attention")
     mode = _attn_mode
     mask, p_attn = None, 0.0
-    if mode == "reference":
+    if kind == "causal":
+        mask = keep
+    elif keep is not None:
+        raise ValueError("simple_attention: keep is the key / value mask of kind='causal'")
+    elif mode == "reference":
         p_attn = 0.5
     elif mode == "replay":
         if not _attn_masks:
@@ -594,11 +638,10 @@ class CrossAttentionFn(Function):
     @staticmethod
     def forward(ctx, query, key, value, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, cfg, mask):
         (kind, h, norm_mask, eps, sign, p_attn, p_out, need_w, token_norm, share) = cfg
-        if kind not in ("galerkin", "linear", "fourier", "softmax"):
+        if kind not in ("galerkin", "linear", "fourier", "softmax", "causal"):
             raise ValueError(f"cross_attention: kind={kind!r}")
-        if token_norm and (kind in ("fourier", "softmax") or norm_mask != 0b110 or gamma is None or beta is None):
+        if token_norm and (kind in ("fourier", "softmax", "causal") or norm_mask != 0b110 or gamma is None or beta is None):
             raise ValueError("cross_attention: token_norm is the K, V norm of the galerkin / linear kinds")
-        H.need_f32_cuda(query, key, value, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, mask)
         groups = _CROSS_GROUPS[share]
         xs = {"none": (query, key, value), "kv": (query, key, key), "qk": (query, query, value)}[share]
         B, n, d = query.shape
@@ -608,6 +651,11 @@ class CrossAttentionFn(Function):
         Dr, DP = dk + p, H.round4(dk + p)
         dev = query.device
         assert kind in ("galerkin", "linear") or n == m, (kind, n, m)      # (cross_attention refuses it with its reason)
+        keep = None
+        if kind == "causal":
+            H.causal_check(DP)
+            keep, mask = mask, None     # the keep vector [B, n_kv] (uint8) travels in the mask slot
+        H.need_f32_cuda(query, key, value, pos, wqkv, bqkv, gamma, beta, wfc, bfc, res, mask)
         if (kind == "linear" or token_norm) and not H.linattn_supported(dk, p):
             raise H.GtNotSupported(f"cross_attention: head size d_k={dk}, pos_dim={p} has no softmax / token-norm kernel")
         if kind == "softmax" and DP not in H.SOFTMAX_DP + H.SOFTMAX_DP_WIDE:
@@ -645,12 +693,14 @@ class CrossAttentionFn(Function):
                                          n_kv=m)
         elif kind == "softmax":
             attn_w, core, ctx.flash = _softmax_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn, d_out, dims, sign, need_w)
+        elif kind == "causal":
+            attn_w, core = _causal_fwd(Qp, Kp, Vp, keep, out, rc, wf, bfc, d_out, dims, sign)
         else:
             attn_w, core, (ctx.flash, ctx.f16, ctx.block16) = _fourier_fwd(Qp, Kp, Vp, out, rc, wf, bfc, mask, d_attn,
                                                                            d_out, dims, sign, need_w)
         _save_named(ctx, wq=wq, gamma=gamma, x0=xcs[0], x1=xcs[1], x2=xcs[2], proj0=projs[0], proj1=projs[1],
                     proj2=projs[2], st0=stats[0], st1=stats[1], st2=stats[2], t0=tiles[0], t1=tiles[1], t2=tiles[2],
-                    kvn_k=kvn_k, kvn_v=kvn_v, st_k=st_k, st_v=st_v, mask=mask, **core)
+                    kvn_k=kvn_k, kvn_v=kvn_v, st_k=st_k, st_v=st_v, mask=mask, keep=keep, **core)
         ctx.cfg, ctx.dims, ctx.n_kv, ctx.salt = cfg, dims, m, salt
         ctx.has = (bqkv is not None, bfc is not None, res is not None)
         attn_w = attn_w.detach()
@@ -675,6 +725,8 @@ class CrossAttentionFn(Function):
             dO3, _, dwfc, dbfc = _galerkin_bwd(kind, s, g, d_attn, ctx.dims, sign, hbf, token_norm, False, False, n_kv=m)
         elif kind == "softmax":
             dO3, dwfc, dbfc = _softmax_bwd(s, g, d_attn, ctx.dims, sign, hbf, ctx.flash)
+        elif kind == "causal":
+            dO3, dwfc, dbfc = _causal_bwd(s, g, ctx.dims, sign, hbf)
         else:
             dO3, dwfc, dbfc = _fourier_bwd(s, g, d_attn, ctx.dims, sign, hbf, ctx.flash, ctx.f16, ctx.block16)
         dgamma = dbeta = None
@@ -715,14 +767,21 @@ class CrossAttentionFn(Function):
 
 def cross_attention(query, key, value, pos, wqkv, bqkv, gamma, beta, wfc, bfc, *, kind: str, n_head: int, norm_mask: int,
                     eps: float, res=None, sign: float = 1.0, p_out: float = 0.0, need_weights: bool = True,
-                    token_norm: bool = False):
+                    token_norm: bool = False, keep=None):
     """Attention block over query [B, n_q, d] and key, value [B, n_kv, d] that are not one tensor; ``res`` must be
     ``query`` (or None).  Returns (out [B, n_q, d], attn_weight).  galerkin / linear: any n_q, n_kv (with ``pos`` they are
     equal), M = (K'^T V') / n_q -- the sum over the n_kv memory tokens, the divisor the QUERY count (layers.py:719, 728).
     fourier / softmax: n_q == n_kv, else NotImplementedError.  ``key is value`` and ``query is key`` are projected as one
-    product and their input receives one summed gradient.  The attention dropout modes act as in simple_attention."""
+    product and their input receives one summed gradient.  The attention dropout modes act as in simple_attention.
+    kind='causal': n_q == n_kv (AssertionError otherwise: the reference's reshape needs it too), ``keep`` [B, n_kv] (uint8) or
+    None masks the memory tokens, no attention dropout, attn_weight None."""
     check_cross_shapes(query, key, value, pos)
     _check_res_is_x(res, query, "cross_attention")
+    if kind == "causal":
+        assert query.size(1) == key.size(1), \
+            f"cross_attention: kind='causal' needs n_q == n_kv (got {query.size(1)}, {key.size(1)})"
+    elif keep is not None:
+        raise ValueError("cross_attention: keep is the key / value mask of kind='causal'")
     if kind in ("fourier", "softmax") and query.size(1) != key.size(1):
         raise NotImplementedError(f"cross_attention: kind={kind!r} with n_q={query.size(1)} != n_kv={key.size(1)}: the fused "
                                   "kernels take one token count")
@@ -731,7 +790,9 @@ def cross_attention(query, key, value, pos, wqkv, bqkv, gamma, beta, wfc, bfc, *
     share = "kv" if key is value else ("qk" if query is key else "none")
     mode = _attn_mode
     mask, p_attn = None, 0.0
-    if mode == "reference":
+    if kind == "causal":
+        mask = keep
+    elif mode == "reference":
         p_attn = 0.5
     elif mode == "replay":
         if not _attn_masks:
@@ -749,3 +810,63 @@ def cross_attention(query, key, value, pos, wqkv, bqkv, gamma, beta, wfc, bfc, *
     out, w = CrossAttentionFn.apply(query, key if share != "qk" else None, value if share != "kv" else None, pos, wqkv, bqkv,
                                     gamma, beta, wfc, bfc, res, cfg, mask)
     return out, (w if w.numel() else None)
+
+
+# ----------------------------------------------------------------------------------- the causal core alone
+class CausalLinearAttnFn(Function):
+    """causal_linear_attn (layers.py:736-762) on [B, h, n, D] tensors: the tensors are laid out as token-major head tiles
+    [B*n, h, round4(D)] with zero pad columns (a torch copy), then gt_causal_attn_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, keep, eps):
+        B, h, n, D = q.shape
+        DP = H.round4(D)
+        H.causal_check(DP)
+        H.need_f32_cuda(q, k, v)
+
+        def tile(t):
+            out = torch.zeros(B, n, h, DP, dtype=torch.float32, device=t.device)
+            out[..., :D] = t.permute(0, 2, 1, 3)
+            return out.reshape(B * n, h, DP)
+        Q, K, V = tile(q), tile(k), tile(v)
+        O, den, states = H.causal_attn_fwd(Q, K, V, keep, B, n, h, DP, eps)
+        _save_named(ctx, Q=Q, K=K, V=V, O=O, keep=keep, den=den, states=states)
+        ctx.dims, ctx.eps = (B, h, n, D, DP), eps
+        return O.reshape(B, n, h, DP)[..., :D].permute(0, 2, 1, 3).contiguous()
+
+    @staticmethod
+    def backward(ctx, gy):
+        B, h, n, D, DP = ctx.dims
+        s = _saved(ctx)
+        dO = torch.zeros(B, n, h, DP, dtype=torch.float32, device=gy.device)
+        dO[..., :D] = gy.permute(0, 2, 1, 3)
+        dQ, dK, dV = H.causal_attn_bwd(dO.reshape(B * n, h, DP), s.O, s.Q, s.K, s.V, s.keep, s.den, s.states, B, n, h, DP, D,
+                                       ctx.eps)
+        dq, dk, dv = (t.reshape(B, n, h, DP)[..., :D].permute(0, 2, 1, 3).contiguous() for t in (dQ, dK, dV))
+        return dq, dk, dv, None, None
+
+
+def check_kv_mask(kv_mask, B: int, n: int):
+    """The key / value mask of the causal kind: None or a torch.bool tensor [B, n], True = keep.  Returns the keep vector
+    (uint8 view) or None; TypeError / AssertionError before anything is launched."""
+    if kv_mask is None:
+        return None
+    if not (isinstance(kv_mask, torch.Tensor) and kv_mask.dtype == torch.bool):
+        raise TypeError("causal attention: the mask is a torch.bool tensor [B, n_kv] (True = keep), got "
+                        f"{getattr(kv_mask, 'dtype', type(kv_mask).__name__)}")
+    assert tuple(kv_mask.shape) == (B, n), f"causal attention: the mask is [B, n_kv] = {(B, n)}, got {tuple(kv_mask.shape)}"
+    return kv_mask.contiguous().view(torch.uint8)
+
+
+def causal_linear_attention(q, k, v, kv_mask=None, eps: float = 1e-7):
+    """The reference's causal_linear_attn on q, k, v [B, h, n, D] (k is not modified): with k^_j = keep_j k_j / n and
+    v^_j = keep_j v_j,  out_i = (sum_{j<=i} k^_j v^_j^T)^T q_i / ((sum_{j<=i} k^_j + eps) . q_i).  ``kv_mask``: torch.bool
+    [B, n], True = keep, or None.  Linear in n (gt_causal_attn_*), differentiable in q, k, v.  No dropout is drawn on the
+    running state, which is never formed; returns (out, None).  The operator is only as well-conditioned as its
+    denominators: with sign-indefinite q, k they cancel and fp32 (here as in torch) loses accuracy accordingly.
+    round4(D) outside H.CAUSAL_DP raises GtNotSupported before anything is launched."""
+    assert q.dim() == 4 and q.shape == k.shape == v.shape, "causal_linear_attention: q, k, v are [B, h, n, D] alike"
+    B, h, n, D = q.shape
+    H.causal_check(H.round4(D))
+    keep = check_kv_mask(kv_mask, B, n)
+    return CausalLinearAttnFn.apply(q, k, v, keep, float(eps)), None

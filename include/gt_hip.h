@@ -1052,6 +1052,36 @@ int gt_graphattn_bwd_col(const void* bitsT, const float* w0, const float* s, con
 int gt_graphattn_weights(const void* bits, const float* w0, const float* s, const float* t, int64_t ldst, const float* L,
                          float* Pm, int32_t B, int32_t n, float alpha, const gt_dropout* drop, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Causal linear attention (gt_causal.hip; reference layers.py:736-762), additive to ABI 21.  Per (sample, head) on head
+ * tiles Q, K, V [B*n, h, DP] (token-major, zero pad columns) and an optional keep vector keep [B, n] of bytes (0 = the key /
+ * value token is dropped; NULL keeps all):
+ *     k^_j = keep_j k_j / n,  v^_j = keep_j v_j,  S_i = sum_{j<=i} k^_j v^_j^T,  z_i = sum_{j<=i} k^_j
+ *     den_i = sum_d (z_i[d] + eps) q_i[d],        O_i = S_i^T q_i / den_i
+ * i.e. A = tril(Q K^^T), O = A V^ / (rowsum(A) + eps sum_d q).  No attention dropout.  Linear in n: chunks of 64 tokens,
+ * three stages per direction (chunk sums, an exclusive scan over the chunks in chunk order, the per-chunk product); neither
+ * the n x n matrix nor the [n, DP, DP] running state reaches HBM.
+ *   gt_causal_attn_fwd   writes O [B*n, h, DP], den [B, h, n] and `states`: per (sample, head, chunk) the exclusive prefix
+ *                        [S_prev (DP x DP) | z_prev (DP)], gt_causal_attn_state_bytes = 4 B h ceil(n / 64) (DP^2 + DP)
+ *                        bytes.  The backward READS them (they are kept, not recomputed): the caller keeps the buffer.
+ *   gt_causal_attn_bwd   with g_i = dO_i / den_i, c_i = -(dO_i . O_i) / den_i, R_j = sum_{i>=j} q_i g_i^T, r_j = sum_{i>=j}
+ *                        c_i q_i:  dQ_i = S_i g_i + c_i (z_i + eps),  dK_j = keep_j / n (R_j v^_j + r_j),  dV_j = keep_j
+ *                        R_j^T k^_j.  D <= DP is the number of real columns: columns D .. DP-1 of dQ, dK, dV are written
+ *                        as exact zeros, and so are the rows of dK, dV at dropped tokens.  Scratch `ws` of
+ *                        gt_causal_attn_bwd_ws_bytes = state bytes + 4 B h n bytes.
+ * DP in {16, 32, 48, 64, 96} and {20, 36, 52, 68, 100}; any other width: GT_ENOTSUP (the size queries return 0), never a
+ * nearest instance.  fp32 arithmetic on v_mfma_f32_16x16x4_f32 whatever the GEMM precision mode.  Plain pointers, the caller's
+ * stream, no allocation, no synchronisation, graph-capturable; no atomics, fixed summation orders: bit-identical from run to
+ * run.  Tiles and their gradients 16-byte aligned.  B, h > 65535 or a non-positive size: GT_EINVAL; a short buffer: GT_EWS.
+ * ------------------------------------------------------------------------------------------- */
+int64_t gt_causal_attn_state_bytes(int32_t B, int32_t n, int32_t h, int32_t DP);
+int64_t gt_causal_attn_bwd_ws_bytes(int32_t B, int32_t n, int32_t h, int32_t DP);
+int gt_causal_attn_fwd(const float* Q, const float* K, const float* V, const uint8_t* keep, float* O, float* den, int32_t B,
+                       int32_t n, int32_t h, int32_t DP, float eps, float* states, int64_t states_bytes, void* stream);
+int gt_causal_attn_bwd(const float* dO, const float* O, const float* Q, const float* K, const float* V, const uint8_t* keep,
+                       const float* den, const float* states, float* dQ, float* dK, float* dV, int32_t B, int32_t n,
+                       int32_t h, int32_t DP, int32_t D, float eps, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

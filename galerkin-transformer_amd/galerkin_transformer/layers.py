@@ -665,15 +665,7 @@ class SimpleAttention(nn.Module):
         """res + sign*dropout(attention(x)); the encoder layer's entry point.  ``need_weights=False`` lets the
         Fourier and softmax types run fused (no n x n matrix in HBM; the returned weight is None).  ``kv_mask``: the
         causal type's key / value mask (torch.bool [B, n], True = keep)."""
-        pos, wfc, bfc, kind = self._operator_args(pos, x.device)
-        keep = self._keep_vector(kv_mask, x)
-        wqkv, bqkv, gamma, beta, mask = self._packed()
-        out, w = ops.simple_attention(x, pos, wqkv, bqkv, gamma, beta, wfc, bfc,
-                                      kind=kind, n_head=self.n_head, norm_mask=mask, eps=self.eps,
-                                      res=residual, sign=sign, p_out=p_out, need_weights=need_weights,
-                                      token_norm=self.add_norm and self.norm_type == "instance", keep=keep)
-        self.attn_weight = w
-        return out, w
+        return self._fused(ops.simple_attention, (x,), x, pos, kv_mask, residual, sign, p_out, need_weights)
 
     def fused_forward_cross(self, query, key, value, pos=None, residual=None, sign=1.0, p_out=0.0, need_weights=True,
                             kv_mask=None):
@@ -681,13 +673,18 @@ class SimpleAttention(nn.Module):
         res + sign*dropout(attention(query, key, value)) with ``residual`` = ``query`` or None.  Shape contracts are
         AssertionErrors, raised before anything is launched."""
         ops.check_cross_shapes(query, key, value, pos if self.pos_dim > 0 else None)
-        pos, wfc, bfc, kind = self._operator_args(pos, query.device)
+        return self._fused(ops.cross_attention, (query, key, value), key, pos, kv_mask, residual, sign, p_out, need_weights)
+
+    def _fused(self, operator, inputs, key, pos, kv_mask, residual, sign, p_out, need_weights):
+        """fused_forward / fused_forward_cross behind their own checks: ``operator`` (ops.simple_attention or
+        ops.cross_attention) on ``inputs`` with this module's packed parameters; ``key`` is what ``kv_mask`` masks."""
+        pos, wfc, bfc, kind = self._operator_args(pos, inputs[0].device)
         keep = self._keep_vector(kv_mask, key)
         wqkv, bqkv, gamma, beta, mask = self._packed()
-        out, w = ops.cross_attention(query, key, value, pos, wqkv, bqkv, gamma, beta, wfc, bfc,
-                                     kind=kind, n_head=self.n_head, norm_mask=mask, eps=self.eps,
-                                     res=residual, sign=sign, p_out=p_out, need_weights=need_weights,
-                                     token_norm=self.add_norm and self.norm_type == "instance", keep=keep)
+        out, w = operator(*inputs, pos, wqkv, bqkv, gamma, beta, wfc, bfc,
+                          kind=kind, n_head=self.n_head, norm_mask=mask, eps=self.eps,
+                          res=residual, sign=sign, p_out=p_out, need_weights=need_weights,
+                          token_norm=self.add_norm and self.norm_type == "instance", keep=keep)
         self.attn_weight = w
         return out, w
 

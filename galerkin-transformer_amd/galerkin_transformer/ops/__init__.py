@@ -20,9 +20,10 @@ One module per operator family; this file only re-exports (every name is the obj
                  library convolution with a reproducible weight gradient, ``edge_conv``
 ``loss``         the weighted-L2 / H1 objectives per sample: ``H1Loss2dFn`` (2-D), ``H1Loss1dFn`` (1-D)
 ``rfattn``       random-feature attention ('rfa' / 'favor'): ``RandomFeatureAttentionFn``, ``random_feature_attention``
-``attention``    the attention-dropout mode and mask queue, ``SimpleAttentionFn`` with its projection stage and cores,
-                 ``CrossAttentionFn`` on the same cores, ``multihead_attention`` (nn.MultiheadAttention's arithmetic),
-                 ``causal_linear_attention`` (the causal core alone on [B, h, n, D] tensors)
+``attention``    the attention-dropout mode, mask queue and call setup; ``AttnConfig``, the core table ``_CORES`` (kind ->
+                 forward and backward core) with its checks and per-call namespace; ``SimpleAttentionFn`` with its
+                 projection stage, ``CrossAttentionFn`` on the same table, ``multihead_attention`` (nn.MultiheadAttention's
+                 arithmetic), ``causal_linear_attention`` (the causal core alone on [B, h, n, D] tensors)
 """
 from ._handoff import (_fold_masks, _fold_seq, _gate_depth, _gate_fold, _hint_output_mask, _mask_hints,  # noqa: F401
                        _masked_twins, _offer_gate, _offer_twin, _relu_mask_sink, _scaler_mask_sink, _silu_gates,

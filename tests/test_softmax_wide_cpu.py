@@ -128,10 +128,28 @@ def test_cpu_call_reaches_the_operator(d_model, n_head, pos_dim):
 
 
 def test_gate_lists_both_sets_and_still_refuses_44():
-    """The operator's width gate.  A call without a device stops at the device check in front of it, so here the gate is
-    read off the operator's source; test_softmax_wide_gpu.py calls it (DP = 44 raises before any launch)."""
-    import inspect
-    from galerkin_transformer import _hip, ops
-    src = inspect.getsource(ops.SimpleAttentionFn.forward)
-    assert "DP not in H.SOFTMAX_DP + H.SOFTMAX_DP_WIDE" in src and "no kernel" in src
+    """The operator's width gate.  A call without a device stops at the device check in front of it, so here the check
+    function that both attention nodes call behind that check is called itself; test_softmax_wide_gpu.py goes through the
+    operator (DP = 44 raises before any launch)."""
+    from galerkin_transformer import _hip
+    from galerkin_transformer.ops import attention as A
+    cfg = A._config("softmax", 2, 0b011, 1e-5, 1.0, 0.5, 0.0, False, False, "self")
+
+    def check(who, dk, p, nopos_ok):
+        A._check_config(who, cfg, dk, p, ("n", 8), None, None, nopos_ok=nopos_ok)
+
     assert 44 not in _hip.SOFTMAX_DP + _hip.SOFTMAX_DP_WIDE
+    for who, nopos_ok in (("simple_attention", True), ("cross_attention", False)):
+        with pytest.raises(_hip.GtNotSupported, match="no kernel") as e:
+            check(who, 40, 4, nopos_ok)                                       # DP = 44
+        assert str(_hip.SOFTMAX_DP) in str(e.value) and str(_hip.SOFTMAX_DP_WIDE) in str(e.value)
+        for DP in _hip.SOFTMAX_DP + _hip.SOFTMAX_DP_WIDE:
+            for p in (1, 2, 3, 4):
+                check(who, DP - 4, p, nopos_ok)
+    # without coordinates: the self node takes the tail-free widths (ops.multihead_attention), the cross node does not
+    for dk in _hip.SOFTMAX_DP_NOPOS:
+        check("simple_attention", dk, 0, True)
+        with pytest.raises(_hip.GtNotSupported, match="no kernel"):
+            check("cross_attention", dk, 0, False)
+    with pytest.raises(_hip.GtNotSupported, match="no kernel"):
+        check("simple_attention", 40, 0, True)                                # 40 is in neither set

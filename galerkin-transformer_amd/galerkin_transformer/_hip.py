@@ -1442,15 +1442,17 @@ def galerkin_ktv_supported(dk: int, p: int) -> bool:
     return not (dk % 16 or dk > 96 or dk // 16 == 5 or p > 2)
 
 
-def galerkin_ktv(Kp: torch.Tensor, Vp: torch.Tensor, B: int, n: int, h: int, dk: int, p: int, gamma=None, beta=None):
+def galerkin_ktv(Kp: torch.Tensor, Vp: torch.Tensor, B: int, n: int, h: int, dk: int, p: int, gamma=None, beta=None,
+                 n_slabs: Optional[int] = None):
     """K'^T V' partial slabs [n_slabs, B, h, DP, DP] from head tiles [B*n, h, DP]; None if the streaming kernel
     does not cover this head size (caller falls back to the batched GEMM).  gamma, beta [2, h, dk]: the tiles are
-    "plain" (normalised values without the LayerNorm affine, gt_hip.h: hn_plain) and the affine is applied on load."""
+    "plain" (normalised values without the LayerNorm affine, gt_hip.h: hn_plain) and the affine is applied on load.
+    n_slabs: token chunks per sample (default: gt_galerkin_ktv_slabs)."""
     need_f32_cuda(Kp, Vp, gamma, beta)
     if not galerkin_ktv_supported(dk, p):
         return None
     DP = round4(dk + p)
-    ns = lib().gt_galerkin_ktv_slabs(B, n)
+    ns = lib().gt_galerkin_ktv_slabs(B, n) if n_slabs is None else int(n_slabs)
     slabs = torch.empty(ns, B, h, DP, DP, dtype=torch.float32, device=Kp.device)
     _launch("gt_galerkin_ktv_affine", Kp, Vp, gamma, beta, B, n, h, dk, p, slabs, ns, key="gt_galerkin_ktv",
             flops=2.0 * B * h * n * DP * DP, nbytes=8.0 * B * n * h * DP, shape=(B, n, h, dk, p))

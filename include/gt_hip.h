@@ -363,7 +363,12 @@ int gt_headtile_bwd(const float* d_out, const float* X, int64_t ldx, const float
  * gt_headnorm_fwd writes): token rows go from HBM straight into MFMA operand registers, the dk x dk core
  * accumulates on the matrix pipe and the p-wide coordinate borders on the VALU.  Writes n_slabs partial
  * [B,h,DP,DP] slabs (token chunks) that gt_galerkin_finalize_fwd sums.  dk % 16 == 0, dk <= 96, p <= 2
- * (else GT_ENOTSUP: use gt_gemm).  gt_galerkin_ktv_slabs suggests n_slabs. */
+ * (else GT_ENOTSUP: use gt_gemm).  gt_galerkin_ktv_slabs suggests n_slabs.
+ * Chunks: chunk = round4(ceil(n / n_slabs)); slab q [n_slabs][B][h][DP][DP] sums the tokens
+ * [q chunk, min(n, (q + 1) chunk)) of its sample -- a chunk is in general no multiple of the kernels' 16-token tile -- and
+ * a chunk that starts at or past n is an all-zero slab.
+ * Slab = [pos | K']^T [pos | V'] on the leading Dr = dk + p rows and columns, exact zeros behind them.  The coordinates
+ * of BOTH operands are read from the K tile (columns 0..p-1 of Kp); the coordinate columns of Vp are not read. */
 int32_t gt_galerkin_ktv_slabs(int32_t B, int32_t n);
 int gt_galerkin_ktv(const float* Kp, const float* Vp, int32_t B, int32_t n, int32_t h, int32_t dk, int32_t p,
                     float* slabs, int32_t n_slabs, void* stream);

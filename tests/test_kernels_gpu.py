@@ -5,6 +5,7 @@ import os
 import pytest
 import torch
 
+import _galerkin_ref as G
 from _util import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -1361,6 +1362,9 @@ def test_plain_head_tiles_ktv_and_dkv_ln(H, gpu_device, B, n, h, dk, p):
     got = H.galerkin_ktv(Kx, Vx, B, n, h, dk, p, gamma=gamma, beta=beta)
     torch.cuda.synchronize()
     assert rel_l2(got.sum(0), ref.sum(0)) < 2e-6
+    # ... and `ref` itself against float64, per element and per slab (tests/_galerkin_ref.py): not kernel against kernel only
+    ref64, E = G.ktv_ref(Kp.cpu(), Vp.cpu(), B, n, h, dk, p, ref.shape[0])
+    assert G.gate_violation(ref.cpu(), ref64, E, "ktv") is None, G.gate_violation(ref.cpu(), ref64, E, "ktv")
     dM = rnd(B, h, DP, DP, dev=dev, seed=610, scale=0.2)
     dQp = rnd(T, h, DP, dev=dev, seed=611)
     ref = H.galerkin_dkv_ln(Kp, Vp, dM, dQp, qkv, gamma, stats, B, n, h, dk, p)
